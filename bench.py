@@ -14,8 +14,8 @@ resident in HBM before timing.  Scaling is STRONG (the north star's "10k-node x
 2k-process fleet interval" at 1/2/4/8 GPUs): the fixed fleet is cut into N node
 ranges by shard.plan_node_ranges (balanced process rows) and every rank
 generates and owns only its range (node snapshots are independent), so N GPUs
-share one 20M-row interval.  At N > 1 a weak-scaling line (a full 10k-node shard
-per GPU) is added as `weak_scaling`; `--scaling weak` makes it the headline.
+share one 20M-row interval.  At N > 1 `--full` adds a weak-scaling line (a full 10k-node
+shard per GPU) as `weak_scaling`; `--scaling weak` makes it the headline.
 `--shard-of W` runs rank 0's shard of a W-way split on one GPU (the per-GPU step
 of a W-GPU run).  Only the cluster totals cross GPUs: per-namespace and cluster
 node totals, all-reduced by the library's own RCCL communicator
@@ -24,6 +24,12 @@ kacc_allreduce_sums per --allreduce-every steps on the comm stream — the C ABI
 cgo caller uses; at N = 1 the same calls run with a one-rank communicator).  torch.distributed
 (gloo) is only the control plane: rank-0 unique-id broadcast, barriers,
 max-over-ranks timing.
+
+A plain run sets up, warms up, times `--steps` steps and prints the headline (metric, value,
+unit, ms_per_step, ...).  `--full` adds what takes runs of its own: the kernel-timing pass
+(kernel_ms, totals_compute_ms), the roofline, the CPU baseline, the scrape, slot-layout,
+pipeline and host-path lines, the weak-scaling line.  `--dump-outputs DIR` writes what the
+last timed step left for a caller (state tables, cluster totals) as DIR/<name>.npy.
 
 Prints ONE JSON line on rank 0.  Launch with N > 1 as
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
@@ -49,6 +55,10 @@ HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md, chip tabl
 # past it the export stores cost more than the launch they save
 FUSED_MAX_NODES = 2048
 METRIC = "process attributions/sec + achieved HBM GB/s, 10k-node fleet, 1/2/4/8 MI355X"
+# --dump-outputs: at most this many elements of one array (1 MiB as float64; 31 tables + 4 totals
+# stay far below 64 MB), a larger one as DUMP_CHUNKS ranges at seeded places
+DUMP_TABLE_ELEMS = 1 << 17
+DUMP_CHUNKS = 64
 
 
 def parse():
@@ -117,9 +127,9 @@ def parse():
                          "the comm stream wait for it every step (the N > 1 handoff without RCCL, ablation)")
     ap.add_argument("--step-events", choices=["separate", "inline", "markers"], default="separate",
                     help="how the kernels are timed with HIP events: separate = the timed region has NO event "
-                         "packet between its kernels (value, ms_per_step) and a second timed pass over the same "
-                         "number of steps right after it carries a start/stop pair on the dispatch packets of each "
-                         "step's interval and totals launches (kacc_time_next_launch) -> kernel_ms, "
+                         "packet between its kernels (value, ms_per_step) and, with --full, a second timed pass "
+                         "over the same number of steps right after it carries a start/stop pair on the dispatch "
+                         "packets of each step's interval and totals launches (kacc_time_next_launch) -> kernel_ms, "
                          "totals_compute_ms; inline = those launch events inside the timed region; markers = "
                          "hipEventRecord markers around them inside the timed region (round 2).  Every event "
                          "packet costs a stream gap: ~9 us per step, profiles/r03/events")
@@ -129,6 +139,16 @@ def parse():
     ap.add_argument("--totals-probe", choices=["both", "ns", "nodes"], default="both",
                     help="ablation: only the namespace sums (ns) or only the cluster node totals (nodes) per step")
     ap.add_argument("--json-out", default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline (set-up, warm-up, the timed steps, the result line) also measure "
+                         "everything that takes runs of its own: the kernel-timing pass (kernel_ms, "
+                         "totals_compute_ms), the roofline (same-box copy, PMC traffic), the CPU baseline, the "
+                         "scrape, slot-layout, pipeline and host-path lines, and at N > 1 the weak-scaling line "
+                         "(each still has its own --no-... switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what their last step left for a caller — the engine's state "
+                         "tables and that step's cluster totals — as DIR/<name>.npy in float64 (tables above "
+                         "DUMP_TABLE_ELEMS elements: a fixed, seeded sample of ranges; rank 0's shard)")
     return ap.parse_args()
 
 
@@ -757,6 +777,44 @@ def host_path_ticks_line(args, steps=10, nbuf=3, mode="full"):
                     f"overlap, {nbuf} staging buffers; the join's churn is fleet.ProcChurn (2 %)"}
 
 
+def dump_ranges(total, key):
+    """The element ranges [(first, count), ...] of an array of `total` elements that
+    --dump-outputs keeps: all of it up to DUMP_TABLE_ELEMS, else DUMP_CHUNKS equal ranges at
+    places drawn from a generator seeded by `key` (the same places in every run and build)."""
+    if total <= DUMP_TABLE_ELEMS:
+        return [(0, total)]
+    from kepler_amd import fleet
+
+    chunk = DUMP_TABLE_ELEMS // DUMP_CHUNKS
+    rng = np.random.default_rng([fleet.SEED, 0xD0, key])
+    at = np.sort(rng.choice(total // chunk, size=DUMP_CHUNKS, replace=False))
+    return [(int(a) * chunk, chunk) for a in at]
+
+
+def dump_outputs(path, w, last):
+    """--dump-outputs: what a caller of the timed path holds after step `last`, the timed
+    region's last — every state table of the engine (kacc_table_download; the derived powers
+    included) and that step's cluster totals (namespace and node sums, all-reduced) — one
+    float64 .npy per array, the ranges of dump_ranges."""
+    import torch
+
+    from kepler_amd import accel
+
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    for t, (name, _) in enumerate(accel.TABLES):
+        _, total = w.acc.table_info(name)
+        parts = [w.acc.download(name, first, count) for first, count in dump_ranges(total, t)]
+        np.save(os.path.join(path, name + ".npy"), np.concatenate(parts).astype(np.float64))
+    b = last % w.n_bufs
+    totals = (("cluster_ns_energy", w.ns_e[b], np.uint64), ("cluster_ns_power", w.ns_p[b], np.float64),
+              ("cluster_node_energy", w.nd_e[b], np.uint64), ("cluster_node_power", w.nd_p[b], np.float64))
+    for k, (name, dev, dtype) in enumerate(totals):
+        a = dev.cpu().numpy().view(dtype).reshape(-1)
+        parts = [a[first:first + count] for first, count in dump_ranges(a.size, len(accel.TABLES) + k)]
+        np.save(os.path.join(path, name + ".npy"), np.concatenate(parts).astype(np.float64))
+
+
 def bench_nodes(config, world, nodes=None, scaling="strong"):
     """Fleet size of a config at `world` GPUs.  Strong scaling (the north star's "10k-node x
     2k-process fleet interval" at 1/2/4/8 GPUs): one fixed fleet cut into `world` node ranges.
@@ -886,14 +944,21 @@ def allreduce_groups(first, n, group):
 
 
 def total_steps(args):
-    """Warm-up steps, the timed steps and (--step-events separate) the kernel-timing pass: every
-    step has its own node counters / clocks (monotonic, as a node's RAPL readings)."""
-    return args.warmup + args.steps * (2 if args.step_events == "separate" else 1)
+    """Warm-up steps, the timed steps and (--full, --step-events separate) the kernel-timing
+    pass: every step has its own node counters / clocks (monotonic, as a node's RAPL readings)."""
+    return args.warmup + args.steps * (2 if timing_pass(args) else 1)
 
 
-def measure(args, w, rank, world, stream, comm_stream):
+def timing_pass(args):
+    """--full with --step-events separate: a second timed pass carries the kernels' events."""
+    return args.full and args.step_events == "separate"
+
+
+def measure(args, w, rank, world, stream, comm_stream, after_timed=None):
     """W untimed warm-up steps, then exactly `steps` steps bracketed by barrier + synchronize;
-    returns (max wall seconds over ranks, per-interval kernel ms of the launch stream).  A step =
+    returns (max wall seconds over ranks, per-interval kernel ms of the launch stream; none
+    without --full unless --step-events puts the events inside the timed region).
+    after_timed(last step) runs right after the timed region, before any timing pass.  A step =
     K intervals (one kacc_run_intervals call) + the cluster totals (partial sums on the compute
     stream, the RCCL all-reduce on the comm stream overlapping the next step).  The host side of
     a step is a handful of C calls with prebuilt arguments: at a 1/8 shard a step is ~60 us of
@@ -1067,7 +1132,9 @@ def measure(args, w, rank, world, stream, comm_stream):
         finish_fused(args.warmup - 1)
     acc.sync(stream)
     torch.cuda.synchronize()
-    tevs = [tuple(torch.cuda.Event(enable_timing=True) for _ in range(4)) for _ in range(args.steps)]
+    last = args.warmup + args.steps - 1  # the timed region's last step
+    events = args.step_events != "separate" or timing_pass(args)
+    tevs = [tuple(torch.cuda.Event(enable_timing=True) for _ in range(4)) for _ in range(args.steps if events else 0)]
     markers = args.step_events == "markers"
     if not markers:  # torch creates an event on its first record; the library re-records it
         for ev in tevs:
@@ -1076,10 +1143,15 @@ def measure(args, w, rank, world, stream, comm_stream):
         torch.cuda.synchronize()
     hev = tevs if markers else [tuple(ctypes.c_void_p(e.cuda_event) for e in ev) for ev in tevs]
     if args.step_events == "separate":
-        wall = timed(args.warmup)  # the timed region: kernels and totals only
-        wall_ev = timed(args.warmup + args.steps, hev)  # kernel timing: the same steps with launch events
+        wall = wall_ev = timed(args.warmup)  # the timed region: kernels and totals only
+        if after_timed:
+            after_timed(last)
+        if events:
+            wall_ev = timed(args.warmup + args.steps, hev)  # kernel timing: the same steps with launch events
     else:
         wall = wall_ev = timed(args.warmup, hev, markers)
+        if after_timed:
+            after_timed(last)
     if w.fused_sums:  # one launch per step: interval + the previous step's sums (no totals launch)
         kernel_ms = [a.elapsed_time(b) / K for a, b, _, _ in tevs]
         totals_ms = []
@@ -1141,21 +1213,25 @@ def main():
     w.acc.sync(stream)
     del prime_t
     log(rank, f"[bench] setup {time.time() - t_setup:.1f}s")
-    wall_max, kernel_ms, totals_ms, wall_ev = measure(args, w, rank, world, stream, comm_stream)
+    dump = None
+    if args.dump_outputs and rank == 0:
+        dump = lambda last: dump_outputs(args.dump_outputs, w, last)  # noqa: E731
+    wall_max, kernel_ms, totals_ms, wall_ev = measure(args, w, rank, world, stream, comm_stream, dump)
 
-    # same-box reference for the roofline: a 1.28 GB device-to-device copy
-    src = torch.empty(160 * 1024 * 1024, dtype=torch.float64, device="cuda")
-    dst = torch.empty_like(src)
-    cps = []
-    for _ in range(5):
-        c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        c0.record()
-        dst.copy_(src)
-        c1.record()
-        c1.synchronize()
-        cps.append(c0.elapsed_time(c1))
-    copy_gbps = 2 * src.numel() * 8 / (float(np.median(cps[1:])) * 1e-3) / 1e9
-    del src, dst
+    copy_gbps = None
+    if args.full:  # same-box reference for the roofline: a 1.28 GB device-to-device copy
+        src = torch.empty(160 * 1024 * 1024, dtype=torch.float64, device="cuda")
+        dst = torch.empty_like(src)
+        cps = []
+        for _ in range(5):
+            c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            c0.record()
+            dst.copy_(src)
+            c1.record()
+            c1.synchronize()
+            cps.append(c0.elapsed_time(c1))
+        copy_gbps = 2 * src.numel() * 8 / (float(np.median(cps[1:])) * 1e-3) / 1e9
+        del src, dst
 
     procs_t = torch.tensor([sizes["n_procs"], sizes["n_nodes"]], dtype=torch.float64)
     if world > 1:
@@ -1171,10 +1247,6 @@ def main():
     # the timed region's first launch carries no earlier step's sums (its last step's sums run
     # as a launch of their own, untimed): steps - 1 of the `steps` timed launches move them
     bytes_per_launch += sums_bytes * (args.steps - 1) / args.steps
-    k_avg_ms = float(np.mean(kernel_ms))
-    achieved = bytes_per_launch / (k_avg_ms * 1e-3) / 1e9
-
-    traffic, traffic_source = pmc_traffic(args, sizes, K, fused, w.fused_sums)
     rccl_version, rccl_path = accel.Cluster.rccl()
     emulated = args.shard_of > 1
     result = {
@@ -1223,21 +1295,29 @@ def main():
                            f"totals all-reduced over RCCL inside libkepler_accel",
         },
         "node_snapshots_per_s": total_nodes_done * K * args.steps / wall_max,
-        "kernel_ms": k_avg_ms,
-        "kernel_ms_steps": [round(x, 5) for x in kernel_ms],
-        "step_minus_kernel_ms": wall_max * 1e3 / args.steps - k_avg_ms * K,
-        # the partial-sum kernel (launch) / interval end -> its end; fused: inside kernel_ms
-        "totals_compute_ms": float(np.mean(totals_ms)) if totals_ms else None,
-        "kernel_timing": {
-            "step_events": args.step_events,
-            "ms_per_step_timing_pass": wall_ev * 1e3 / args.steps,
-            "note": ("timed region without event packets; kernel_ms / totals_compute_ms from HIP events on the "
-                     "dispatch packets of the interval and totals launches (kacc_time_next_launch, the launch "
-                     "stream) over a second timed pass of the same number of steps right after it"
-                     if args.step_events == "separate" else
-                     "HIP events inside the timed region (" + args.step_events + ")"),
-        },
-        "roofline": {
+    }
+    if kernel_ms:  # --full, or --step-events inline / markers (events inside the timed region)
+        k_avg_ms = float(np.mean(kernel_ms))
+        result.update({
+            "kernel_ms": k_avg_ms,
+            "kernel_ms_steps": [round(x, 5) for x in kernel_ms],
+            "step_minus_kernel_ms": wall_max * 1e3 / args.steps - k_avg_ms * K,
+            # the partial-sum kernel (launch) / interval end -> its end; fused: inside kernel_ms
+            "totals_compute_ms": float(np.mean(totals_ms)) if totals_ms else None,
+            "kernel_timing": {
+                "step_events": args.step_events,
+                "ms_per_step_timing_pass": wall_ev * 1e3 / args.steps,
+                "note": ("timed region without event packets; kernel_ms / totals_compute_ms from HIP events on the "
+                         "dispatch packets of the interval and totals launches (kacc_time_next_launch, the launch "
+                         "stream) over a second timed pass of the same number of steps right after it"
+                         if args.step_events == "separate" else
+                         "HIP events inside the timed region (" + args.step_events + ")"),
+            },
+        })
+    if args.full:
+        achieved = bytes_per_launch / (k_avg_ms * 1e-3) / 1e9
+        traffic, traffic_source = pmc_traffic(args, sizes, K, fused, w.fused_sums)
+        result["roofline"] = {
             "bound": "hbm",
             "achieved": achieved,
             "peak": HBM_PEAK_GBPS,
@@ -1252,15 +1332,15 @@ def main():
             "export_sums_bytes": sums_bytes,
             "same_box_copy_GBps": copy_gbps,
             "frac_of_copy": achieved / copy_gbps,
-        },
-        "rccl": {"version": rccl_version, "path": rccl_path},
-        "cpu_baseline": None,
-    }
+        }
+    result["rccl"] = {"version": rccl_version, "path": rccl_path}
+    if args.full:
+        result["cpu_baseline"] = None
     if emulated:
         result["note"] = (f"one GPU running rank 0's shard of the {split}-way split: the per-GPU step of an "
                           f"{split}-GPU strong-scaling run without the cross-GPU all-reduce (one-rank communicator)")
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not emulated:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not emulated:
         res, cs_ = cpu_baseline(layout, [w.prime] + w.full, w.node_steps, args.cpu_nodes, args.cpu_seconds,
                                 max_runs=args.cpu_runs)
         gf = res["gofaithful"]
@@ -1291,7 +1371,7 @@ def main():
                                          "affinity mask, shared with the other GPUs' jobs"},
         }
         result["cpu_baseline"]["gpu_over_cpu"] = result["value"] / gf["value"]
-    if world == 1:
+    if args.full and world == 1:
         try:
             result["scrape_powers"] = scrape_line(w.acc, w.sizes["n_procs"], Z)
         except Exception as e:  # a secondary line: report, never lose the headline
@@ -1310,7 +1390,7 @@ def main():
     w.close()
     del w
 
-    if world > 1 and scaling == "strong" and args.weak_line and args.config in (1, 2, 3, 5):
+    if args.full and world > 1 and scaling == "strong" and args.weak_line and args.config in (1, 2, 3, 5):
         # extra key: every rank a full shard of its own (weak scaling), the same timed loop
         pick_totals(bench_nodes(args.config, world, args.nodes, "weak") // world)
         wk = Workload(args, bench_nodes(args.config, world, args.nodes, "weak"), world, rank, rank, world, local, K,
@@ -1330,7 +1410,8 @@ def main():
         wk.close()
         del wk
 
-    if world == 1 and args.frag_line > 0 and args.fragment == 0 and args.config in (1, 2, 3) and not emulated:
+    if (args.full and world == 1 and args.frag_line > 0 and args.fragment == 0 and args.config in (1, 2, 3)
+            and not emulated):
         try:
             result["slot_layouts"] = slot_layout_lines(args, args.frag_line, K, min(args.steps, 10),
                                                        bytes_per_launch)
@@ -1346,13 +1427,15 @@ def main():
                         "(KACC_JOIN_REUSE_TERMINATED) returns after 40 intervals of 2 % /proc-shaped churn, "
                         "timed on one context beside pristine slots (slot_layouts)"}
 
-    if world == 1 and args.pipeline_line and args.fragment == 0 and args.config == 3 and K == 1 and not emulated:
+    if (args.full and world == 1 and args.pipeline_line and args.fragment == 0 and args.config == 3 and K == 1
+            and not emulated):
         try:
             result["pipeline"] = pipeline_line(args)
         except Exception as e:  # a secondary line: report, never lose the headline
             result["pipeline"] = {"error": repr(e)}
 
-    if world == 1 and args.host_line and args.fragment == 0 and args.config == 3 and K == 1 and not emulated:
+    if (args.full and world == 1 and args.host_line and args.fragment == 0 and args.config == 3 and K == 1
+            and not emulated):
         try:
             result["host_path"] = host_path_line(args)
         except Exception as e:  # a secondary line: report, never lose the headline

@@ -126,3 +126,37 @@ def test_bench_allreduce_groups():
         gs = bench.allreduce_groups(first, n, g)
         assert [k for a, b in gs for k in range(a, b + 1)] == list(range(first, first + n))
         assert all(b - a + 1 <= max(1, g) for a, b in gs) and gs[-1][0] == gs[-1][1]
+
+
+def test_bench_plain_run_times_only_its_steps():
+    """A plain run prepares warm-up + `--steps` steps; the kernel-timing pass (as many steps
+    again, --step-events separate) exists only under --full."""
+    from types import SimpleNamespace
+
+    import bench
+
+    args = SimpleNamespace(warmup=3, steps=20, step_events="separate", full=False)
+    assert not bench.timing_pass(args) and bench.total_steps(args) == 23
+    args.full = True
+    assert bench.timing_pass(args) and bench.total_steps(args) == 43
+    args.step_events = "inline"  # events inside the timed region: no second pass either way
+    assert not bench.timing_pass(args) and bench.total_steps(args) == 23
+
+
+def test_bench_dump_ranges():
+    """--dump-outputs: a small array whole; a large one as DUMP_CHUNKS disjoint ranges of
+    DUMP_TABLE_ELEMS elements in all, inside the array, the same in every run (seeded by the
+    array's key), so two builds dump the same places."""
+    import bench
+
+    cap, chunks = bench.DUMP_TABLE_ELEMS, bench.DUMP_CHUNKS
+    assert 35 * cap * 8 <= 64 * 1000 * 1000  # 31 tables + 4 totals within the 64 MB budget
+    assert bench.dump_ranges(0, 0) == [(0, 0)]
+    assert bench.dump_ranges(cap, 3) == [(0, cap)]
+    for total in (cap + 1, cap + cap // chunks, 80_000_000):
+        r = bench.dump_ranges(total, 12)
+        assert r == bench.dump_ranges(total, 12)
+        assert len(r) == chunks and sum(c for _, c in r) == cap
+        assert all(f0 + c0 <= f1 for (f0, c0), (f1, _) in zip(r, r[1:]))  # ascending, disjoint
+        assert r[0][0] >= 0 and r[-1][0] + r[-1][1] <= total
+    assert bench.dump_ranges(80_000_000, 12) != bench.dump_ranges(80_000_000, 13)

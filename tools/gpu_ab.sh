@@ -9,7 +9,7 @@ mkdir -p gpurun_out/$O
 timeout -k 10 900 python -u -m pytest ${TESTS:-tests -m gpu} -x -q --timeout 240 --timeout-method thread -p no:cacheprovider \
   > gpurun_out/$O/pytest_gpu.log 2>&1 || { echo "pytest failed rc=$?"; tail -40 gpurun_out/$O/pytest_gpu.log; exit 1; }
 tail -n 1 gpurun_out/$O/pytest_gpu.log
-B="--no-cpu-baseline --frag-line 0 --no-pipeline-line --no-host-line"
+B="--full --no-cpu-baseline --frag-line 0 --no-pipeline-line --no-host-line"
 args=()
 for r in $(seq 1 ${REPS:-2}); do
   for v in base main; do

@@ -13,5 +13,7 @@ timeout -k 10 200 python -c 'import __graft_entry__ as g; g.smoke()' > gpurun_ou
 tail -1 gpurun_out/$O/smoke.log
 OUT=$O/pmc CONFIGS="3 1 5" bash tools/gpu_pmc_traffic.sh || exit $?
 cp gpurun_out/$O/pmc/pmc_traffic.json profiles/pmc_traffic.json
-timeout -k 10 600 python bench.py --json-out gpurun_out/$O/bench_c3.json > gpurun_out/$O/bench_c3.log 2>&1 || exit $?
-tail -1 gpurun_out/$O/bench_c3.log | cut -c1-600
+J=${JSON_DIR:-bench_json}/$O
+mkdir -p $J
+timeout -k 10 600 python bench.py --full --json-out $J/bench_c3.json > $J/bench_c3.log 2>&1 || exit $?
+tail -1 $J/bench_c3.log | cut -c1-600

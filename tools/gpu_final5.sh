@@ -42,8 +42,8 @@ run() {  # NAME SECONDS bench-args...
     || { echo "bench $n rc=$?"; tail -5 gpurun_out/$O/bench_$n.log; exit 1; }
   tail -n 1 gpurun_out/$O/bench_$n.log | cut -c1-400
 }
-run c3 600
-run c1 300 --config 1 --no-cpu-baseline
-run c5 400 --config 5 --intervals 60 --no-cpu-baseline
-run s8 300 --shard-of 8 --steps 50 --warmup 10 $B
-run s8_handoff 300 --shard-of 8 --steps 48 --warmup 8 --comm-wait always --allreduce-every 8 $B
+run c3 600 --full
+run c1 300 --full --config 1 --no-cpu-baseline
+run c5 400 --full --config 5 --intervals 60 --no-cpu-baseline
+run s8 300 --full --shard-of 8 --steps 50 --warmup 10 $B
+run s8_handoff 300 --full --shard-of 8 --steps 48 --warmup 8 --comm-wait always --allreduce-every 8 $B

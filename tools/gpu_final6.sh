@@ -46,11 +46,11 @@ run() {  # NAME SECONDS bench-args...
   tail -n 1 gpurun_out/$O/bench_$n.log | cut -c1-400
 }
 if [ "${PART:-a}" = b ]; then
-run c3 600
-run c1 300 --config 1 --no-cpu-baseline
-run c5 400 --config 5 --intervals 60 --no-cpu-baseline
-run s8 300 --shard-of 8 --steps 50 --warmup 10 $B
-run s8_handoff 300 --shard-of 8 --steps 48 --warmup 8 --comm-wait always --allreduce-every 8 $B
+run c3 600 --full
+run c1 300 --full --config 1 --no-cpu-baseline
+run c5 400 --full --config 5 --intervals 60 --no-cpu-baseline
+run s8 300 --full --shard-of 8 --steps 50 --warmup 10 $B
+run s8_handoff 300 --full --shard-of 8 --steps 48 --warmup 8 --comm-wait always --allreduce-every 8 $B
 # the slot join: per-phase times (stops 1..8), the round-5 kernel (511) beside production (-1)
 # and the first cuckoo build (25087), the per-wave SQ counters of the same three, then the
 # production kernel's SQ counters per phase stop

@@ -14,14 +14,14 @@ mkdir -p "$O"
 step() { local n=$1 s=$2; shift 2; echo "== $n"; (cd /tmp && timeout -k 10 "$s" "$@") > "$O/$n.log" 2>&1; local rc=$?; echo "== $n rc=$rc"; tail -2 "$O/$n.log"; [ $rc -eq 0 ] || exit $rc; }
 run() {  # name build config-args...
   local name=$1 build=$2; shift 2
-  local dir=$R env=()
+  local dir=$R env=() full=--full
   case $build in
-    r2) dir=$R/ab_prev/r2 ;;
+    r2) dir=$R/ab_prev/r2 full= ;;  # that tree's bench.py measures everything by default
     main) ;;
     *) env=(KACC_LIB=$R/kepler_amd/lib/r4var/libkepler_accel_$build.so) ;;
   esac
   step "$name" 300 env "${env[@]}" rocprofv3 --kernel-trace --stats --output-format csv -d "$O/$name" -o run -- \
-    python3 "$dir/bench.py" "$@" --no-cpu-baseline --frag-line 0 --json-out "$O/$name.json"
+    python3 "$dir/bench.py" $full "$@" --no-cpu-baseline --frag-line 0 --json-out "$O/$name.json"
 }
 for r in ${ROUNDS:-1 2}; do
   for b in r2 main ${VARS:-}; do

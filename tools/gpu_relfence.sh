@@ -11,7 +11,7 @@ timeout -k 10 400 python -u -m pytest tests/test_gpu_cluster.py -m gpu -x -q --t
   -p no:cacheprovider > gpurun_out/$O/pt_cluster.log 2>&1; rc=$?
 echo "cluster tests rc=$rc: $(tail -1 gpurun_out/$O/pt_cluster.log)"
 [ $rc -eq 0 ] || { tail -30 gpurun_out/$O/pt_cluster.log; exit $rc; }
-B="python bench.py --steps 40 --warmup 5 --no-cpu-baseline --frag-line 0 --no-pipeline-line --shard-of 8"
+B="python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --frag-line 0 --no-pipeline-line --shard-of 8"
 args=()
 for r in 1 2; do
   args+=($O/s8_def_r$r 300 "$B --json-out gpurun_out/$O/s8_def_r$r.json")

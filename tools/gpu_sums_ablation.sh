@@ -10,7 +10,7 @@ mkdir -p gpurun_out/$O
 timeout -k 10 300 python -u -m pytest ${TESTS:-tests/test_gpu_export_sums.py tests/test_gpu_cluster.py} -x -q --timeout 120 \
   --timeout-method thread -p no:cacheprovider > gpurun_out/$O/pytest.log 2>&1 || { echo "pytest rc=$?"; tail -30 gpurun_out/$O/pytest.log; exit 1; }
 tail -1 gpurun_out/$O/pytest.log
-B="--no-cpu-baseline --frag-line 0 --no-pipeline-line --no-host-line"
+B="--full --no-cpu-baseline --frag-line 0 --no-pipeline-line --no-host-line"
 args=()
 for w in ${SIZES:-s8 s4 c3}; do
   case $w in
