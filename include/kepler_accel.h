@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define KACC_ABI_VERSION 5u
+#define KACC_ABI_VERSION 6u
 #define KACC_MAX_ZONES 8u
 
 /* Status codes. */
@@ -863,6 +863,76 @@ int kacc_format_lines(kacc_ctx *ctx, kacc_table t, uint64_t first, uint64_t coun
                       const char *const *zone_names, const uint32_t *zone_order, uint32_t n_zones,
                       const char *labels, const uint64_t *label_off, const uint32_t *row_order,
                       uint64_t *line_off, char *out, uint64_t out_cap, uint64_t *total, void *stream);
+
+/* ---- top consumers of the running workloads (ABI 6) -------------------------
+ * Which running workloads draw the most, per node and across the context's
+ * fleet, selected on the device: the export of a fleet is a selection, not the
+ * whole table.  No reference call is replaced (Kepler exports every running
+ * workload; the ranking is PromQL's topk).  Both calls work on the running rows
+ * of ONE workload kind exactly as the caller's last interval batch lists them.
+ *
+ * t is one of the eight workload tables KACC_T_{PROC,CTR,VM,POD}_{ENERGY,POWER}
+ * (the table implies the kind), zone < Z, 1 <= k <= KACC_TOP_MAX.  The value of
+ * a row is its slot's element of t in `zone`, exactly as kacc_table_download /
+ * kacc_table_read of t return it: an energy in µJ, or Usage.Power (derived for
+ * processes, containers and VMs; the stored record for pods).
+ *
+ * ORDER — the whole contract.  Every value has a u64 sort key:
+ *   - an energy table: the u64 value itself;
+ *   - a power table, for the f64 p with bits b:
+ *       NaN                -> 0 (below every number, as PromQL's topk ranks it)
+ *       p == 0 (+0 or -0)  -> the key of +0.0, 1<<63
+ *       p > 0              -> b | 1<<63
+ *       p < 0              -> ~b
+ * Lists run in DESCENDING key order; equal keys go in ASCENDING batch row
+ * order.  The per-node list of node n is the first min(k, rows) of node n's
+ * rows in that order; the fleet list is the first min(k, rows) of the rows of
+ * all listed nodes in that order (batch row indices are global: one total
+ * order).  out_row is the batch row index, out_slot the row's slot (its slot
+ * word & KACC_SLOT_MASK; kacc_unpack takes it as it is), out_node the row's
+ * node, out_value the table's own value (µJ, or the bits of the f64 µW: a -0.0
+ * stays -0.0, a NaN keeps its bits).  Entries past the count hold 0xffffffff in
+ * row, slot and node and 0 in value, so the whole output is deterministic.
+ *
+ * VALIDITY — that of the derived tables (kacc_table): the rows must be those of
+ * each node's last processed interval, and the call must be ordered after that
+ * interval and before the context's next one (the same stream, or events).  A
+ * node's guard operands (ActivePower, activeEnergy, ProcessTotalCPUTimeDelta)
+ * are read once for the node that lists the row, not through KACC_T_*_NODE:
+ * the same bits for rows that satisfy the rule.  A node flagged
+ * KACC_NODE_READ_ERROR kept its previous snapshot, which this batch does not
+ * describe: it lists nothing (count 0, its entries filled as above), and the
+ * caller keeps that node's previous list.
+ *
+ * ERRORS — KACC_EINVAL (nothing is launched) for a table that is not one of
+ * the eight, zone >= Z, k outside 1 .. KACC_TOP_MAX, n_nodes > the context's
+ * nodes, or a NULL ctx / rows / row_off / slot / out_count / out_row.  On the
+ * device every index is clamped: a row whose slot & KACC_SLOT_MASK is past the
+ * kind's capacity is left out, and so are the rows of a node whose row range is
+ * not inside [0, n_rows); either raises KACC_ERANGE at kacc_sync (bit 512 of
+ * the device error word, "top list").  Such a batch never faults.
+ *
+ * Asynchronous on `stream` (NULL = the context's stream): nothing is read
+ * back, and the fleet call's scratch memory is stream-ordered.               */
+#define KACC_TOP_MAX 1024u
+typedef struct kacc_top_rows {      /* one kind's rows of the interval batch (DEVICE pointers) */
+  uint32_t n_nodes, n_rows;         /* n_rows = row_off[n_nodes]                               */
+  const uint32_t *row_off;          /* [n_nodes+1] the batch's proc_off / ctr_off / vm_off / pod_off */
+  const uint32_t *slot;             /* [n_rows] slot words (KACC_SLOT_NEW is ignored)          */
+  const uint32_t *node_status;      /* [n_nodes] or NULL: a KACC_NODE_READ_ERROR node lists nothing */
+} kacc_top_rows;
+/* One list per node of the batch. */
+int kacc_top_nodes(kacc_ctx *ctx, kacc_table t, uint32_t zone, uint32_t k, const kacc_top_rows *rows,
+                   uint32_t *out_count,   /* [n_nodes]      min(k, node's rows)                 */
+                   uint32_t *out_row,     /* [n_nodes * k]  batch row index                     */
+                   uint32_t *out_slot,    /* [n_nodes * k]  or NULL                             */
+                   uint64_t *out_value,   /* [n_nodes * k]  or NULL: µJ, or the bits of the f64 µW */
+                   void *stream);
+/* One list over all listed nodes; out_slot, out_node and out_value may be NULL. */
+int kacc_top_fleet(kacc_ctx *ctx, kacc_table t, uint32_t zone, uint32_t k, const kacc_top_rows *rows,
+                   uint32_t *out_count,   /* [1] min(k, rows of all listed nodes)               */
+                   uint32_t *out_row, uint32_t *out_slot, uint32_t *out_node, uint64_t *out_value, /* [k] */
+                   void *stream);
 
 /* Algorithmic HBM bytes of K consecutive intervals of these sizes: K times
  * kacc_interval_bytes, or (carried != 0: kacc_run_intervals' one-launch path,

@@ -19,7 +19,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KACC_LIB", os.path.join(_HERE, "lib", "libkepler_accel.so"))  # KACC_LIB: A/B builds
 
-KACC_ABI_VERSION = 5
+KACC_ABI_VERSION = 6
 KACC_MAX_ZONES = 8
 KACC_OK = 0
 KACC_EINVAL = -1
@@ -53,6 +53,7 @@ KACC_MEDIUM_MAX_AGGREGATES = 256
 KACC_UNIQUE_ID_BYTES = 128
 KACC_PROC_REGULAR, KACC_PROC_CONTAINER, KACC_PROC_VM = 0, 1, 2
 KACC_KEY_TOMB = 0xFFFFFFFFFFFFFFFE
+KACC_TOP_MAX = 1024  # largest k of kacc_top_nodes / kacc_top_fleet
 
 # kacc_table enum, in header order: (name, numpy dtype)
 TABLES = [
@@ -102,6 +103,8 @@ TABLE_INDEX = {name: i for i, (name, _) in enumerate(TABLES)}
 EXPORTS = [
     "kacc_format_values",
     "kacc_format_lines",
+    "kacc_top_nodes",
+    "kacc_top_fleet",
     "kacc_zone_agg_create",
     "kacc_zone_agg_destroy",
     "kacc_zone_agg_read",
@@ -267,6 +270,12 @@ class KaccExportSums(ctypes.Structure):
                                 "out_node_energy", "out_node_power")]
 
 
+class KaccTopRows(ctypes.Structure):
+    """kacc_top_rows: one workload kind's rows of the interval batch (kacc_top_nodes / kacc_top_fleet)."""
+    _fields_ = [("n_nodes", c_uint32), ("n_rows", c_uint32)] + [
+        (n, c_void_p) for n in ("row_off", "slot", "node_status")]
+
+
 KACC_TICKS_ESCAPED = 0xFFFF
 KACC_USER_HZ = 100
 
@@ -332,6 +341,8 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.kacc_batch_alloc.argtypes = [c_void_p, POINTER(KaccShape), POINTER(c_void_p), POINTER(POINTER(KaccInterval))]
     lib.kacc_pack.argtypes = [POINTER(KaccRecords), POINTER(KaccPacked), c_uint32]
     lib.kacc_unpack.argtypes = [c_void_p, c_int, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.kacc_top_nodes.argtypes = [c_void_p, c_int, c_uint32, c_uint32, POINTER(KaccTopRows)] + [c_void_p] * 5
+    lib.kacc_top_fleet.argtypes = [c_void_p, c_int, c_uint32, c_uint32, POINTER(KaccTopRows)] + [c_void_p] * 6
     lib.kacc_last_error_copy.argtypes = [c_void_p, c_char_p, ctypes.c_size_t]
     lib.kacc_last_error_copy.restype = ctypes.c_size_t
     lib.kacc_create_multi.argtypes = [POINTER(c_int), c_int, POINTER(KaccConfig), POINTER(c_void_p),
@@ -680,6 +691,24 @@ class Accel:
         """kacc_unpack: per-workload energy / power rows out of the state tables (device pointers)."""
         self._check(self.lib.kacc_unpack(self.ctx, kind, n, c_void_p(slot_words_ptr), c_void_p(dest_ptr or None),
                                          c_void_p(out_energy_ptr), c_void_p(out_power_ptr), c_void_p(stream or None)))
+
+    def top_nodes(self, table: str, zone: int, k: int, rows: KaccTopRows, out_count_ptr: int, out_row_ptr: int,
+                  out_slot_ptr: int = 0, out_value_ptr: int = 0, stream: int = 0) -> None:
+        """kacc_top_nodes: per node of the batch, its min(k, rows) running workloads with the highest
+        value of `table` in `zone` (device pointers; count [n_nodes], the lists [n_nodes * k])."""
+        self._check(self.lib.kacc_top_nodes(self.ctx, TABLE_INDEX[table], zone, k, ctypes.byref(rows),
+                                            c_void_p(out_count_ptr or None), c_void_p(out_row_ptr or None),
+                                            c_void_p(out_slot_ptr or None), c_void_p(out_value_ptr or None),
+                                            c_void_p(stream or None)))
+
+    def top_fleet(self, table: str, zone: int, k: int, rows: KaccTopRows, out_count_ptr: int, out_row_ptr: int,
+                  out_slot_ptr: int = 0, out_node_ptr: int = 0, out_value_ptr: int = 0, stream: int = 0) -> None:
+        """kacc_top_fleet: the min(k, rows) running workloads of all listed nodes with the highest value
+        of `table` in `zone` (device pointers; count [1], the lists [k])."""
+        self._check(self.lib.kacc_top_fleet(self.ctx, TABLE_INDEX[table], zone, k, ctypes.byref(rows),
+                                            c_void_p(out_count_ptr or None), c_void_p(out_row_ptr or None),
+                                            c_void_p(out_slot_ptr or None), c_void_p(out_node_ptr or None),
+                                            c_void_p(out_value_ptr or None), c_void_p(stream or None)))
 
     def namespace_totals(self, n_ns: int, ns_pod_off_ptr: int, ns_pod_slot_ptr: int,
                          out_energy_ptr: int, out_power_ptr: int, stream: int = 0) -> None:
