@@ -46,6 +46,9 @@
 extern "C" {
 #endif
 
+/* Still 6 with kacc_tracker_read and kacc_format_lines_dev: they are new symbols
+ * only (no struct, no existing signature or result changed), so a client built
+ * against an earlier ABI-6 header runs unchanged.                              */
 #define KACC_ABI_VERSION 6u
 #define KACC_MAX_ZONES 8u
 
@@ -800,6 +803,49 @@ int kacc_tracker_add(kacc_tracker *t, const kacc_slotmap *m, const uint64_t *ter
  * in node order, each node's items highest energy first.                    */
 int kacc_tracker_items(kacc_tracker *t, uint32_t *count, uint64_t *key, uint32_t *node,
                        uint64_t *energy, double *power);
+/* Items() on the device, for the nodes of a mask: the terminated half of a
+ * scrape (power_collector.go:225-243 writes every workload family twice, the
+ * running set and the terminated trackers' items with state="terminated").
+ * The items and their order are exactly kacc_tracker_items': node by node in
+ * node order, each node's items highest target-zone energy first, restricted
+ * to the listed nodes.
+ *   node_mask: as in kacc_tracker_clear — DEVICE [nodes], nonzero = listed,
+ *     NULL = all; nodes = the tracker's node count, kacc_config.nodes.
+ *   node_off: DEVICE [nodes + 1], always written.  node_off[n] = index of node
+ *     n's first item (an unlisted node contributes none), node_off[nodes] = the
+ *     total.  The caller copies the total back on the same stream, with the
+ *     keys it needs for its label strings.
+ *   out_*: DEVICE, each may be NULL.  Item i's key, node, and frozen per-zone
+ *     energy (µJ) / power (µW) in [i*Z, (i+1)*Z): dense arrays, as
+ *     kacc_format_lines_dev takes them.
+ *   item_cap: capacity of the outputs in items.  When the total exceeds it,
+ *     items [0, item_cap) are written and nothing at or past item_cap;
+ *     node_off still holds the full offsets (size a retry from them), and
+ *     kacc_sync reports KACC_ERANGE (bit 2048 of the device error word,
+ *     "tracker read").  item_cap 0 is the sizing call: only node_off is
+ *     written, no error is raised and nothing is cleared.
+ *   KACC_TRACKER_READ_CLEAR: every listed node's tracker is empty after the
+ *     call, as if kacc_tracker_clear(t, node_mask, stream) were queued behind it
+ *     (process.go:80-84: Clear() after the export) — inside the call's own
+ *     launches.  A call whose total exceeds item_cap clears nothing.
+ * ORDERING: asynchronous on `stream` (NULL = the context's): nothing is read
+ * back, there is no device-wide synchronize, and the scratch memory is
+ * stream-ordered.  The call sees the adds and clears queued on `stream` before
+ * it; adds on ANOTHER stream need an event that `stream` waits for
+ * (kacc_tracker_items needs none: it synchronizes the device).  The next add
+ * or clear of the tracker must in turn be ordered after this call.
+ * A disabled tracker (max_size 0) reads as empty.  On the device every index
+ * is clamped: no input faults.
+ * KACC_EINVAL, nothing launched: NULL t or node_off, unknown flag bits,
+ * item_cap > 0 with all four outputs NULL.                                   */
+#define KACC_TRACKER_READ_CLEAR 0x1u
+int kacc_tracker_read(kacc_tracker *t, const uint32_t *node_mask, uint32_t flags, uint32_t item_cap,
+                      uint32_t *node_off,   /* DEVICE [nodes + 1]                */
+                      uint64_t *out_key,    /* DEVICE [item_cap]     or NULL     */
+                      uint32_t *out_node,   /* DEVICE [item_cap]     or NULL     */
+                      uint64_t *out_energy, /* DEVICE [item_cap * Z] or NULL     */
+                      double *out_power,    /* DEVICE [item_cap * Z] or NULL     */
+                      void *stream);
 
 /* ---- multi-socket aggregated zones ---------------------
  * device.AggregatedZone (internal/device/energy_zone.go:47-148) for every
@@ -863,6 +909,22 @@ int kacc_format_lines(kacc_ctx *ctx, kacc_table t, uint64_t first, uint64_t coun
                       const char *const *zone_names, const uint32_t *zone_order, uint32_t n_zones,
                       const char *labels, const uint64_t *label_off, const uint32_t *row_order,
                       uint64_t *line_off, char *out, uint64_t out_cap, uint64_t *total, void *stream);
+/* The same lines from a dense DEVICE array instead of a table: row i is
+ * elements [i*Z, (i+1)*Z) of src (Z = the context's zones), u64 µJ written as
+ * Joules() when is_energy is nonzero, f64 µW written as Watts() otherwise.
+ * Everything else is kacc_format_lines' contract to the letter with first = 0
+ * and count = rows: row-major lines, row_order, zone_order, labels /
+ * label_off [rows + 1], line_off [rows * n_zones + 1], the sizing call with
+ * out == NULL, KACC_ERANGE when out_cap < *total, synchronous.  Such arrays are
+ * kacc_tracker_read's out_energy / out_power (the terminated workloads, whose
+ * frozen copies have no table row; their labels carry state="terminated") and
+ * kacc_unpack's outputs.  src must be complete on `stream` (the same stream
+ * as the call that wrote it, or an event).                                    */
+int kacc_format_lines_dev(kacc_ctx *ctx, int is_energy, const void *src /* DEVICE [rows * Z] */,
+                          uint64_t rows, const char *name, const char *const *zone_names,
+                          const uint32_t *zone_order, uint32_t n_zones, const char *labels,
+                          const uint64_t *label_off, const uint32_t *row_order, uint64_t *line_off,
+                          char *out, uint64_t out_cap, uint64_t *total, void *stream);
 
 /* ---- top consumers of the running workloads (ABI 6) -------------------------
  * Which running workloads draw the most, per node and across the context's

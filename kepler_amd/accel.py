@@ -54,6 +54,7 @@ KACC_UNIQUE_ID_BYTES = 128
 KACC_PROC_REGULAR, KACC_PROC_CONTAINER, KACC_PROC_VM = 0, 1, 2
 KACC_KEY_TOMB = 0xFFFFFFFFFFFFFFFE
 KACC_TOP_MAX = 1024  # largest k of kacc_top_nodes / kacc_top_fleet
+KACC_TRACKER_READ_CLEAR = 0x1  # kacc_tracker_read: clear the listed nodes' trackers behind the read
 
 # kacc_table enum, in header order: (name, numpy dtype)
 TABLES = [
@@ -103,6 +104,7 @@ TABLE_INDEX = {name: i for i, (name, _) in enumerate(TABLES)}
 EXPORTS = [
     "kacc_format_values",
     "kacc_format_lines",
+    "kacc_format_lines_dev",
     "kacc_top_nodes",
     "kacc_top_fleet",
     "kacc_zone_agg_create",
@@ -113,6 +115,7 @@ EXPORTS = [
     "kacc_tracker_clear",
     "kacc_tracker_add",
     "kacc_tracker_items",
+    "kacc_tracker_read",
     "kacc_pack",
     "kacc_unpack",
     "kacc_slotmap_create",
@@ -334,6 +337,10 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
                                       POINTER(c_char_p), POINTER(ctypes.c_uint32), ctypes.c_uint32,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_uint64,
                                       POINTER(ctypes.c_uint64), c_void_p]
+    lib.kacc_format_lines_dev.argtypes = [c_void_p, ctypes.c_int, c_void_p, ctypes.c_uint64, c_char_p,
+                                          POINTER(c_char_p), POINTER(ctypes.c_uint32), ctypes.c_uint32,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_uint64,
+                                          POINTER(ctypes.c_uint64), c_void_p]
     lib.kacc_run_intervals.argtypes = [c_void_p, POINTER(KaccInterval), ctypes.c_uint32, c_void_p]
     lib.kacc_sync.argtypes = [c_void_p, c_void_p]
     lib.kacc_time_next_launch.argtypes = [c_void_p, c_void_p, c_void_p]
@@ -403,6 +410,7 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.kacc_tracker_clear.argtypes = [c_void_p, c_void_p, c_void_p]
     lib.kacc_tracker_add.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.kacc_tracker_items.argtypes = [c_void_p, POINTER(c_uint32), c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.kacc_tracker_read.argtypes = [c_void_p, c_void_p, c_uint32, c_uint32] + [c_void_p] * 6
     lib.kacc_slotmap_create.argtypes = [c_void_p, c_int, c_uint32, c_void_p, POINTER(c_void_p)]
     lib.kacc_slotmap_destroy.argtypes = [c_void_p]
     lib.kacc_slotmap_destroy.restype = None
@@ -686,6 +694,22 @@ class Accel:
                                                c_void_p(stream or None)))
         return total.value
 
+    def format_lines_dev(self, is_energy: bool, src_ptr: int, rows: int, metric: str, zone_names, labels_ptr: int,
+                         label_off_ptr: int, line_off_ptr: int, out_ptr: int = 0, out_cap: int = 0,
+                         zone_order=None, row_order_ptr: int = 0, stream: int = 0) -> int:
+        """kacc_format_lines_dev: sample lines of a dense device array [rows, Z] (u64 µJ when is_energy,
+        else f64 µW; device pointers); returns the text size."""
+        zn = (c_char_p * len(zone_names))(*[z.encode() for z in zone_names])
+        zo = (ctypes.c_uint32 * len(zone_names))(*zone_order) if zone_order is not None else None
+        total = ctypes.c_uint64(0)
+        self._check(self.lib.kacc_format_lines_dev(self.ctx, int(bool(is_energy)), c_void_p(src_ptr or None), rows,
+                                                   metric.encode(), zn, zo, len(zone_names),
+                                                   c_void_p(labels_ptr or None), c_void_p(label_off_ptr or None),
+                                                   c_void_p(row_order_ptr or None), c_void_p(line_off_ptr or None),
+                                                   c_void_p(out_ptr or None), out_cap, ctypes.byref(total),
+                                                   c_void_p(stream or None)))
+        return total.value
+
     def unpack(self, kind: int, n: int, slot_words_ptr: int, dest_ptr: int, out_energy_ptr: int,
                out_power_ptr: int, stream: int = 0) -> None:
         """kacc_unpack: per-workload energy / power rows out of the state tables (device pointers)."""
@@ -865,6 +889,18 @@ class Tracker:
                                                       e.ctypes.data, p.ctypes.data))
         c = m.value
         return k[:c], nd[:c], e[:c], p[:c]
+
+    def read(self, node_off_ptr: int, item_cap: int = 0, out_key_ptr: int = 0, out_node_ptr: int = 0,
+             out_energy_ptr: int = 0, out_power_ptr: int = 0, node_mask_ptr: int = 0, flags: int = 0,
+             stream: int = 0) -> None:
+        """kacc_tracker_read: Items() of the listed nodes on the device, asynchronous on `stream`
+        (device pointers: node_off u32[nodes + 1]; key u64 / node u32 [item_cap]; energy u64 / power
+        f64 [item_cap, Z]).  item_cap 0 sizes only; flags: KACC_TRACKER_READ_CLEAR."""
+        self.accel._check(self.lib.kacc_tracker_read(self.handle, c_void_p(node_mask_ptr or None), flags, item_cap,
+                                                     c_void_p(node_off_ptr or None), c_void_p(out_key_ptr or None),
+                                                     c_void_p(out_node_ptr or None),
+                                                     c_void_p(out_energy_ptr or None),
+                                                     c_void_p(out_power_ptr or None), c_void_p(stream or None)))
 
     def close(self) -> None:
         if self.handle:

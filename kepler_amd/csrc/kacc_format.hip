@@ -815,26 +815,17 @@ int kacc_format_values(kacc_ctx *ctx, kacc_table t, uint64_t first, uint64_t cou
   return KACC_OK;
 }
 
-int kacc_format_lines(kacc_ctx *ctx, kacc_table t, uint64_t first, uint64_t count, const char *name,
-                      const char *const *zone_names, const uint32_t *zone_order, uint32_t n_zones,
-                      const char *labels, const uint64_t *label_off, const uint32_t *row_order,
-                      uint64_t *line_off, char *out, uint64_t out_cap, uint64_t *total, void *stream) {
-  if (!ctx || t < 0 || t >= KACC_T_COUNT || !total) return KACC_EINVAL;
-  *total = 0;
+}  // extern "C"
+
+namespace {
+
+// The lines of rows [first, first + count) of table t (t >= 0; `energy` as the table
+// is), or of the caller's dense DEVICE array `dense` [count * Z] (t < 0, first 0).
+int format_lines_impl(kacc_ctx *ctx, int t, const void *dense, bool energy, uint64_t first, uint64_t count,
+                      const char *name, const char *const *zone_names, const uint32_t *zone_order, uint32_t n_zones,
+                      const char *labels, const uint64_t *label_off, const uint32_t *row_order, uint64_t *line_off,
+                      char *out, uint64_t out_cap, uint64_t *total, void *stream) {
   const uint32_t Z = ctx->cfg.zones;
-  // workload tables (rows = slots) and the node x zone tables (rows = nodes: the node
-  // families of power_collector.go:246-278, one call per zone for their path label)
-  const bool energy = t == KACC_T_PROC_ENERGY || t == KACC_T_CTR_ENERGY || t == KACC_T_VM_ENERGY ||
-                      t == KACC_T_POD_ENERGY || t == KACC_T_NODE_ENERGY_TOTAL || t == KACC_T_NODE_ACTIVE_TOTAL ||
-                      t == KACC_T_NODE_IDLE_TOTAL;
-  const bool power = t == KACC_T_PROC_POWER || t == KACC_T_CTR_POWER || t == KACC_T_VM_POWER ||
-                     t == KACC_T_POD_POWER || t == KACC_T_NODE_POWER || t == KACC_T_NODE_ACTIVE_POWER ||
-                     t == KACC_T_NODE_IDLE_POWER;
-  if (!energy && !power)
-    return kacc_fail(ctx, KACC_EINVAL, "table %d is not a workload or node energy / power table", (int)t);
-  const uint64_t slots = ctx->counts[t] / Z;
-  if (first > slots || count > slots - first)
-    return kacc_fail(ctx, KACC_EINVAL, "format_lines: rows outside table %d", (int)t);
   if (!name || !zone_names || n_zones == 0 || n_zones > Z)
     return kacc_fail(ctx, KACC_EINVAL, "format_lines: name / zone names missing or n_zones > %u", Z);
   if (count && (!labels || !label_off || !line_off))
@@ -860,7 +851,7 @@ int kacc_format_lines(kacc_ctx *ctx, kacc_table t, uint64_t first, uint64_t coun
   KACC_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
   const uint64_t lines = count * n_zones;
-  a.src = ctx->tables[t];
+  a.src = t >= 0 ? ctx->tables[t] : dense;
   a.Z = Z;
   a.is_energy = energy ? 1u : 0u;
   a.first = first;
@@ -883,7 +874,7 @@ int kacc_format_lines(kacc_ctx *ctx, kacc_table t, uint64_t first, uint64_t coun
   // every sub-buffer 256-B aligned (the scan's look-back state needs aligned storage)
   auto al = [](uint64_t x) { return (x + 255) & ~255ull; };
   const uint64_t off_len = 1024, off_scan = al(off_len + 8 * (lines + 1));
-  const bool derived = kacc_derived_kind(t) >= 0 || t == KACC_T_POD_ENERGY || t == KACC_T_POD_POWER;
+  const bool derived = t >= 0 && (kacc_derived_kind(t) >= 0 || t == KACC_T_POD_ENERGY || t == KACC_T_POD_POWER);
   const uint64_t off_derived = al(off_scan + scan_bytes);
   KACC_HIP(ctx, hipMallocAsync(reinterpret_cast<void **>(&tmp), derived ? off_derived + 8 * count * Z : off_scan + scan_bytes,
                                st));
@@ -906,10 +897,7 @@ int kacc_format_lines(kacc_ctx *ctx, kacc_table t, uint64_t first, uint64_t coun
   const uint64_t g1 = std::min<uint64_t>((lines + kacc::fmt::kThreads - 1) / kacc::fmt::kThreads, 1u << 20);
   hipLaunchKernelGGL(kacc::fmt::line_len_kernel, dim3(static_cast<uint32_t>(g1)), dim3(kacc::fmt::kThreads), 0, st, a);
   uint64_t *tile_sum = reinterpret_cast<uint64_t *>(tmp + off_scan);
-  const dim3 gt(static_cast<uint32_t>(tiles)), bt(kacc::fmt::kScanThreads);
-  hipLaunchKernelGGL(kacc::fmt::scan_tile_sums, gt, bt, 0, st, a.len, lines + 1, tile_sum);
-  hipLaunchKernelGGL(kacc::fmt::scan_tile_prefix, dim3(1), bt, 0, st, tile_sum, tiles);
-  hipLaunchKernelGGL(kacc::fmt::scan_tiles, gt, bt, 0, st, a.len, lines + 1, tile_sum, line_off);
+  (void)kacc_internal_scan_u64(ctx, a.len, lines + 1, tile_sum, line_off, st);
   if (hipGetLastError() != hipSuccess) return done(kacc_fail(ctx, KACC_EHIP, "format_lines: scan launch"));
   if (hipMemcpyAsync(total, line_off + lines, sizeof(uint64_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipStreamSynchronize(st) != hipSuccess)
@@ -924,6 +912,62 @@ int kacc_format_lines(kacc_ctx *ctx, kacc_table t, uint64_t first, uint64_t coun
                      0, st, a);
   if (hipGetLastError() != hipSuccess) rc = kacc_fail(ctx, KACC_EHIP, "format_lines: launch");
   return done(rc);
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t kacc_internal_scan_tiles(uint64_t n) { return (n + kacc::fmt::kTile - 1) / kacc::fmt::kTile; }
+
+int kacc_internal_scan_u64(kacc_ctx *ctx, const uint64_t *in, uint64_t n, uint64_t *tile_sum, uint64_t *out,
+                           void *stream) {
+  const uint64_t tiles = kacc_internal_scan_tiles(n);
+  if (tiles == 0) return KACC_OK;
+  if (tiles > 0x7fffffffull) return kacc_fail(ctx, KACC_EINVAL, "scan: too many values");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 gt(static_cast<uint32_t>(tiles)), bt(kacc::fmt::kScanThreads);
+  hipLaunchKernelGGL(kacc::fmt::scan_tile_sums, gt, bt, 0, st, in, n, tile_sum);
+  hipLaunchKernelGGL(kacc::fmt::scan_tile_prefix, dim3(1), bt, 0, st, tile_sum, tiles);
+  hipLaunchKernelGGL(kacc::fmt::scan_tiles, gt, bt, 0, st, in, n, tile_sum, out);
+  return KACC_OK;
+}
+
+int kacc_format_lines(kacc_ctx *ctx, kacc_table t, uint64_t first, uint64_t count, const char *name,
+                      const char *const *zone_names, const uint32_t *zone_order, uint32_t n_zones,
+                      const char *labels, const uint64_t *label_off, const uint32_t *row_order,
+                      uint64_t *line_off, char *out, uint64_t out_cap, uint64_t *total, void *stream) {
+  if (!ctx || t < 0 || t >= KACC_T_COUNT || !total) return KACC_EINVAL;
+  *total = 0;
+  const uint32_t Z = ctx->cfg.zones;
+  // workload tables (rows = slots) and the node x zone tables (rows = nodes: the node
+  // families of power_collector.go:246-278, one call per zone for their path label)
+  const bool energy = t == KACC_T_PROC_ENERGY || t == KACC_T_CTR_ENERGY || t == KACC_T_VM_ENERGY ||
+                      t == KACC_T_POD_ENERGY || t == KACC_T_NODE_ENERGY_TOTAL || t == KACC_T_NODE_ACTIVE_TOTAL ||
+                      t == KACC_T_NODE_IDLE_TOTAL;
+  const bool power = t == KACC_T_PROC_POWER || t == KACC_T_CTR_POWER || t == KACC_T_VM_POWER ||
+                     t == KACC_T_POD_POWER || t == KACC_T_NODE_POWER || t == KACC_T_NODE_ACTIVE_POWER ||
+                     t == KACC_T_NODE_IDLE_POWER;
+  if (!energy && !power)
+    return kacc_fail(ctx, KACC_EINVAL, "table %d is not a workload or node energy / power table", (int)t);
+  const uint64_t slots = ctx->counts[t] / Z;
+  if (first > slots || count > slots - first)
+    return kacc_fail(ctx, KACC_EINVAL, "format_lines: rows outside table %d", (int)t);
+  return format_lines_impl(ctx, t, nullptr, energy, first, count, name, zone_names, zone_order, n_zones, labels,
+                           label_off, row_order, line_off, out, out_cap, total, stream);
+}
+
+int kacc_format_lines_dev(kacc_ctx *ctx, int is_energy, const void *src, uint64_t rows, const char *name,
+                          const char *const *zone_names, const uint32_t *zone_order, uint32_t n_zones,
+                          const char *labels, const uint64_t *label_off, const uint32_t *row_order,
+                          uint64_t *line_off, char *out, uint64_t out_cap, uint64_t *total, void *stream) {
+  if (!ctx || !total) return KACC_EINVAL;
+  *total = 0;
+  if (rows && !src) return kacc_fail(ctx, KACC_EINVAL, "format_lines: NULL device array");
+  if (rows > 0xffffffffffffffffull / (8ull * ctx->cfg.zones))
+    return kacc_fail(ctx, KACC_EINVAL, "format_lines: too many rows");
+  return format_lines_impl(ctx, -1, src, is_energy != 0, 0, rows, name, zone_names, zone_order, n_zones, labels,
+                           label_off, row_order, line_off, out, out_cap, total, stream);
 }
 
 }  // extern "C"

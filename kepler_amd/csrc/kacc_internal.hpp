@@ -64,6 +64,14 @@ extern "C" int kacc_internal_dense_range(kacc_ctx *ctx, int t, uint64_t first, u
 extern "C" int kacc_internal_pod_scatter(kacc_ctx *ctx, int t, uint64_t first, uint64_t count, const void *in,
                                          void *stream);
 
+// Exclusive scan of n u64 values (device, async on `stream`): the library's own
+// reduce-then-scan of kacc_format.hip (three launches, tiles of 4,096 values).
+// tile_sum: device scratch of kacc_internal_scan_tiles(n) u64 (the tile count,
+// at most 2^31 - 1); out may not alias in.
+extern "C" uint64_t kacc_internal_scan_tiles(uint64_t n);
+extern "C" int kacc_internal_scan_u64(kacc_ctx *ctx, const uint64_t *in, uint64_t n, uint64_t *tile_sum,
+                                      uint64_t *out, void *stream);
+
 // kacc_time_next_launch: while a LaunchTiming scope is alive on this thread,
 // KACC_LAUNCH attaches the scope's start event to the first kernel it launches
 // and its stop event to every one (the last recording wins), through the

@@ -221,6 +221,123 @@ __global__ __launch_bounds__(kThreads) void pack_kernel(const Args a, const uint
   }
 }
 
+// ---- kacc_tracker_read: Items() of the listed nodes, on the device -----------------
+// count -> scan (kacc_internal_scan_u64) -> pack, all on the caller's stream.
+constexpr uint32_t kErrRead = 1u << 11;  // more items than item_cap
+constexpr uint32_t kReadMaxBlocks = 2048;
+
+// The scan's input: cnt[n] = min(size[n], cap) of a listed node, 0 otherwise; cnt[nodes] = 0,
+// so the exclusive scan's last entry is the total.
+__global__ __launch_bounds__(kThreads) void read_count_kernel(const uint32_t *size, const uint32_t *mask,
+                                                              uint32_t n_nodes, uint32_t cap, uint64_t *cnt) {
+  const uint32_t n = blockIdx.x * kThreads + threadIdx.x;
+  if (n > n_nodes) return;
+  cnt[n] = n < n_nodes && (!mask || mask[n]) ? min(size[n], cap) : 0u;
+}
+
+struct ReadArgs {
+  const uint64_t *off;  // [nodes + 1] exclusive scan of the counts
+  const uint64_t *set_key;
+  const uint64_t *set_e;
+  const double *set_p;
+  uint32_t *size;
+  const uint32_t *mask;
+  uint32_t n_nodes, cap, Z, item_cap, clear;
+  uint32_t *node_off;
+  uint64_t *out_key;
+  uint32_t *out_node;
+  uint64_t *out_e;
+  double *out_p;
+  uint32_t *err;
+};
+
+// One round of a wave-wide 64-ary search for the smallest n in [lo, hi] with off[n + 1] > x
+// (off is a scan, so the predicate is monotone; it holds at hi): 64 probes, one per lane, in
+// one round trip; the range shrinks 64-fold.  lo and hi stay wave-uniform.
+__device__ __forceinline__ void node_search_round(const uint64_t *off, uint64_t x, uint32_t lane, uint32_t &lo,
+                                                  uint32_t &hi) {
+  const uint64_t st = (hi - lo) / 64u + 1u;
+  const uint64_t q = min(lo + lane * st + (st - 1), static_cast<uint64_t>(hi));
+  const uint64_t m = __ballot(off[q + 1] > x);
+  const uint64_t b = lo + (m ? static_cast<uint32_t>(__builtin_ctzll(m)) : 63u) * st;
+  const uint32_t nlo = static_cast<uint32_t>(min(b, static_cast<uint64_t>(hi)));
+  const uint32_t nhi = static_cast<uint32_t>(min(b + (st - 1), static_cast<uint64_t>(hi)));
+  lo = __builtin_amdgcn_readfirstlane(nlo);
+  hi = __builtin_amdgcn_readfirstlane(nhi);
+}
+
+// The work is the items, not the nodes: a wave takes 64 consecutive OUTPUT items (grid
+// stride).  It finds the nodes of its first and of its last item in the offsets with the
+// wave-wide search above (3 dependent round trips at 10k nodes instead of a binary
+// search's 14); lane l then finds item c0 + l's node between the two (an upper bound:
+// empty and unlisted nodes are stepped over; a few steps, as 64 items span few nodes) and
+// copies its key and node.  Then the wave copies the items' 64 Z energy (power) words as
+// one contiguous range, lane l taking words kW (64 k + l) .. + kW (kW = 2: 16-B loads
+// and stores, 1 KiB per instruction, for Z = 4 and 16-B aligned outputs; else 8 B), each
+// word's source row taken from its item's lane.  A node's rows are contiguous in the set,
+// so the loads are contiguous per node as well.  Counts come from the offsets only:
+// size[] is not read here, so READ_CLEAR zeroes it in the same launch.  Every index is
+// clamped (the set rows to the node's capacity, the outputs to item_cap).
+using u64x2 = __attribute__((ext_vector_type(2))) unsigned long long;
+template <uint32_t kZ, uint32_t kW>  // zones (0 = a.Z, any), words per lane and copy
+__global__ __launch_bounds__(kThreads) void read_pack_kernel(const ReadArgs a) {
+  static_assert(kW == 1 || (kW == 2 && kZ != 0 && kZ % 2 == 0), "16-B copies need an even, fixed Z");
+  const uint32_t Z = kZ ? kZ : a.Z;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t total = a.off[a.n_nodes];
+  const bool fits = total <= a.item_cap;
+  const uint32_t tid = blockIdx.x * kThreads + threadIdx.x, threads = gridDim.x * kThreads;
+  for (uint64_t n = tid; n <= a.n_nodes; n += threads) {
+    a.node_off[n] = static_cast<uint32_t>(min(a.off[n], static_cast<uint64_t>(0xffffffffu)));
+    if (a.clear && fits && n < a.n_nodes && (!a.mask || a.mask[n])) a.size[n] = 0;
+  }
+  // item_cap 0 is the sizing call; offsets past 32 bits cannot be reported at all
+  if (tid == 0 && !fits && (a.item_cap || total > 0xffffffffull)) atomicOr(a.err, kErrRead);
+  const uint64_t limit = min(total, static_cast<uint64_t>(a.item_cap));
+  const uint64_t step = static_cast<uint64_t>(threads);
+  for (uint64_t c0 = static_cast<uint64_t>(tid - lane); c0 < limit; c0 += step) {  // wave-uniform
+    const uint64_t last = min(c0 + 63, limit - 1);
+    uint32_t la = 0, ha = a.n_nodes - 1, lb = 0, hb = a.n_nodes - 1;  // nodes of items c0 and `last`
+    while (ha > la || hb > lb) {  // the two searches' loads share a round trip
+      node_search_round(a.off, c0, lane, la, ha);
+      node_search_round(a.off, last, lane, lb, hb);
+    }
+    const uint64_t i = min(c0 + lane, last);
+    uint32_t lo = la, hi = max(la, lb);  // the node n with off[n] <= i < off[n + 1]
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (a.off[mid + 1] > i)
+        hi = mid;
+      else
+        lo = mid + 1;
+    }
+    const uint64_t o = a.off[lo];
+    const uint64_t j = min(i >= o ? i - o : 0ull, static_cast<uint64_t>(a.cap - 1));
+    const uint64_t row = static_cast<uint64_t>(lo) * a.cap + j;
+    if (c0 + lane < limit) {
+      if (a.out_key) a.out_key[i] = a.set_key[row];
+      if (a.out_node) a.out_node[i] = lo;
+    }
+    const uint32_t words = static_cast<uint32_t>(last - c0 + 1) * Z;
+    const uint64_t w0 = c0 * Z;
+#pragma unroll
+    for (uint32_t k = 0; k < (kZ ? kZ : KACC_MAX_ZONES) / kW; ++k) {
+      const uint32_t w = (k * 64 + lane) * kW;
+      const uint32_t it = min(w / Z, 63u), z = w - it * Z;
+      const uint64_t r = __shfl(row, static_cast<int>(it), 64);  // every lane takes part
+      if (w < words) {
+        if (kW == 2) {  // z is even and Z is: both words are the item's, 16-B aligned
+          if (a.out_e) *reinterpret_cast<u64x2 *>(a.out_e + w0 + w) = *reinterpret_cast<const u64x2 *>(a.set_e + r * Z + z);
+          if (a.out_p) *reinterpret_cast<u64x2 *>(a.out_p + w0 + w) = *reinterpret_cast<const u64x2 *>(a.set_p + r * Z + z);
+        } else {
+          if (a.out_e) a.out_e[w0 + w] = a.set_e[r * Z + z];
+          if (a.out_p) a.out_p[w0 + w] = a.set_p[r * Z + z];
+        }
+      }
+    }
+  }
+}
+
 // Clear(): every node, or the nodes with mask[n] != 0 (process.go:80-84).
 __global__ __launch_bounds__(kThreads) void clear_kernel(uint32_t *size, uint32_t n_nodes, const uint32_t *mask) {
   const uint32_t n = blockIdx.x * kThreads + threadIdx.x;
@@ -432,6 +549,66 @@ int kacc_tracker_items(kacc_tracker *t, uint32_t *count, uint64_t *key, uint32_t
     if (p) (void)hipFree(p);
   if (e != hipSuccess) return kacc_fail(ctx, KACC_EHIP, "tracker items: %s", hipGetErrorString(e));
   return KACC_OK;
+}
+
+int kacc_tracker_read(kacc_tracker *t, const uint32_t *node_mask, uint32_t flags, uint32_t item_cap,
+                      uint32_t *node_off, uint64_t *out_key, uint32_t *out_node, uint64_t *out_energy,
+                      double *out_power, void *stream) {
+  if (!t || !node_off) return KACC_EINVAL;
+  kacc_ctx *ctx = t->ctx;
+  if (flags & ~KACC_TRACKER_READ_CLEAR) return kacc_fail(ctx, KACC_EINVAL, "tracker read: unknown flags 0x%x", flags);
+  if (item_cap && !out_key && !out_node && !out_energy && !out_power)
+    return kacc_fail(ctx, KACC_EINVAL, "tracker read: item_cap %u and no output array", item_cap);
+  KACC_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  const uint32_t nodes = t->nodes;
+  if (t->max_size == 0) {  // tracker.go:82 disabled: nothing was ever added
+    KACC_HIP(ctx, hipMemsetAsync(node_off, 0, 4ull * (nodes + 1ull), st));
+    return KACC_OK;
+  }
+  // temporaries, stream ordered: the counts, their scan, the scan's tile sums
+  const uint64_t n = nodes + 1ull, tiles = kacc_internal_scan_tiles(n);
+  uint64_t *tmp = nullptr;
+  KACC_HIP(ctx, hipMallocAsync(reinterpret_cast<void **>(&tmp), 8 * (2 * n + tiles), st));
+  uint64_t *cnt = tmp, *off = tmp + n, *tile_sum = tmp + 2 * n;
+  kacc::trk::ReadArgs a{};
+  a.off = off;
+  a.set_key = t->d_set_key;
+  a.set_e = t->d_set_e;
+  a.set_p = t->d_set_p;
+  a.size = t->d_size;
+  a.mask = node_mask;
+  a.n_nodes = nodes;
+  a.cap = t->cap;
+  a.Z = t->Z;
+  a.item_cap = item_cap;
+  a.clear = flags & KACC_TRACKER_READ_CLEAR;
+  a.node_off = node_off;
+  a.out_key = out_key;
+  a.out_node = out_node;
+  a.out_e = out_energy;
+  a.out_p = out_power;
+  a.err = ctx->d_err;
+  (void)hipGetLastError();  // clear a stale error of an earlier call
+  const uint32_t T = kacc::trk::kThreads;
+  hipLaunchKernelGGL(kacc::trk::read_count_kernel, dim3(static_cast<uint32_t>((n + T - 1) / T)), dim3(T), 0, st,
+                     t->d_size, node_mask, nodes, t->cap, cnt);
+  int rc = kacc_internal_scan_u64(ctx, cnt, n, tile_sum, off, st);
+  if (rc == KACC_OK) {
+    // one workgroup per 256 items that can be written, the rest by grid stride
+    const uint64_t bound = std::min<uint64_t>(item_cap, static_cast<uint64_t>(nodes) * t->cap);
+    const uint32_t grid = static_cast<uint32_t>(
+        std::min<uint64_t>(std::max<uint64_t>((bound + T - 1) / T, 1), kacc::trk::kReadMaxBlocks));
+    // 16-B copies for Z = 4 when the caller's arrays allow them (the sets are hipMalloc'ed)
+    const bool wide = a.Z == 4 && ((reinterpret_cast<uintptr_t>(out_energy) | reinterpret_cast<uintptr_t>(out_power)) & 15u) == 0;
+    if (wide)
+      hipLaunchKernelGGL((kacc::trk::read_pack_kernel<4, 2>), dim3(grid), dim3(T), 0, st, a);
+    else
+      hipLaunchKernelGGL((kacc::trk::read_pack_kernel<0, 1>), dim3(grid), dim3(T), 0, st, a);
+    if (hipGetLastError() != hipSuccess) rc = kacc_fail(ctx, KACC_EHIP, "tracker read: launch");
+  }
+  (void)hipFreeAsync(tmp, st);
+  return rc;
 }
 
 }  // extern "C"
