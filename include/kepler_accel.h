@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-/* Still 6 with kacc_tracker_read and kacc_format_lines_dev: they are new symbols
+/* Still 6 with kacc_tracker_read, kacc_format_lines_dev and kacc_select_above: they are new symbols
  * only (no struct, no existing signature or result changed), so a client built
  * against an earlier ABI-6 header runs unchanged.                              */
 #define KACC_ABI_VERSION 6u
@@ -995,6 +995,81 @@ int kacc_top_fleet(kacc_ctx *ctx, kacc_table t, uint32_t zone, uint32_t k, const
                    uint32_t *out_count,   /* [1] min(k, rows of all listed nodes)               */
                    uint32_t *out_row, uint32_t *out_slot, uint32_t *out_node, uint64_t *out_value, /* [k] */
                    void *stream);
+
+/* ---- running workloads above a threshold (ABI 6, additive) -------------------
+ * "Every process above 1 W", "every pod above 10 J": the cut of the RUNNING set
+ * that the trackers' min_energy / max_size make for the terminated one.  The
+ * answer has no fixed size, so it is not a top list: an order-preserving filter
+ * of the rows of ONE workload kind as the caller's last interval batch lists
+ * them, written as the dense arrays kacc_format_lines_dev takes, with per-node
+ * offsets as kacc_tracker_read writes them.  No reference call is replaced
+ * (Kepler exports every running workload; the cut is PromQL's).
+ *
+ * t, zone and rows are kacc_top_*'s: t is one of the eight workload tables (the
+ * table implies the kind), zone < Z, and value(r) is the element of t at (row
+ * r's slot word & KACC_SLOT_MASK, zone), exactly as kacc_table_read returns it
+ * (a derived power for processes, containers and VMs, the stored record for
+ * pods).  threshold holds the same kind of bits as kacc_top_*'s out_value: µJ
+ * for an energy table, the bits of an f64 µW for a power table.
+ *
+ * THE RULE.  Row r is SELECTED iff key(value(r)) >= key(threshold), key being
+ * the u64 sort key of the top lists above (an energy is its own key; a power:
+ * NaN -> 0, ±0 -> 1<<63, p > 0 -> bits | 1<<63, p < 0 -> ~bits).  Consequences:
+ *   - energy threshold 0 selects every listed row;
+ *   - a NaN power threshold selects every listed row (NaN powers included);
+ *   - power threshold +0.0 (or -0.0) selects every non-negative power, both
+ *     zeros included, and no NaN;
+ *   - power threshold bits 1 (the smallest denormal) selects "strictly positive".
+ *
+ * ORDER AND OUTPUTS.  Items are the selected rows in ascending batch row order,
+ * so node by node.  node_off[n] is the index of node n's first item (a node
+ * without items: that of the next one), node_off[n_nodes] the total; the caller
+ * copies it back on the same stream.  Item i carries its batch row (out_row),
+ * its slot (out_slot: the slot word & KACC_SLOT_MASK), its node (out_node) and
+ * the row's EnergyTotal (µJ) and Usage.Power (µW) of ALL Z zones in
+ * [i*Z, (i+1)*Z) of out_energy / out_power: bit for bit what kacc_table_read of
+ * the kind's energy / power table holds at that slot (a -0.0 and a NaN keep
+ * their bits).  Each out_* may be NULL.
+ *
+ * UNLISTED NODES AND VALIDITY.  A node contributes nothing when node_mask
+ * (DEVICE [n_nodes], nonzero = listed; NULL = all) unlists it or
+ * rows->node_status flags it KACC_NODE_READ_ERROR.  The validity rule is the
+ * top lists': the rows are those of each node's last processed interval, and
+ * the call is ordered after that interval and before the context's next one.
+ * A node's guard operands (ActivePower, activeEnergy, ProcessTotalCPUTimeDelta)
+ * are read once for the node that lists the row, not through KACC_T_*_NODE.
+ *
+ * CAPACITY — kacc_tracker_read's contract.  item_cap is the capacity of the
+ * outputs in items.  When the total exceeds it, items [0, item_cap) are written
+ * and nothing at or past item_cap; node_off still holds the full offsets (size
+ * a retry from them), and kacc_sync reports KACC_ERANGE (bit 4096 of the device
+ * error word, "select").  item_cap 0 is the sizing call: only node_off is
+ * written and no error is raised.  Output elements at index >= the total are
+ * never written.
+ *
+ * CLAMPING.  A row whose slot & KACC_SLOT_MASK is past the kind's capacity is
+ * left out, and so are all rows of a node whose row range is not inside
+ * [0, n_rows); either raises KACC_ERANGE at kacc_sync (bit 4096).  No input
+ * faults.
+ *
+ * ERRORS — KACC_EINVAL, nothing launched: a NULL ctx / rows / row_off / slot
+ * (with n_rows > 0) / node_off, a table that is not one of the eight,
+ * zone >= Z, n_nodes > the context's nodes, item_cap > 0 with all five outputs
+ * NULL.
+ *
+ * Asynchronous on `stream` (NULL = the context's): nothing is read back, there
+ * is no device-wide synchronize, and the scratch memory is stream-ordered.    */
+int kacc_select_above(kacc_ctx *ctx, kacc_table t, uint32_t zone, uint64_t threshold,
+                      const kacc_top_rows *rows,      /* the kind's rows of the last interval batch   */
+                      const uint32_t *node_mask,      /* DEVICE [n_nodes], nonzero = listed; NULL=all */
+                      uint32_t item_cap,
+                      uint32_t *node_off,             /* DEVICE [n_nodes + 1], always written         */
+                      uint32_t *out_row,              /* DEVICE [item_cap] or NULL: batch row index   */
+                      uint32_t *out_slot,             /* DEVICE [item_cap] or NULL                    */
+                      uint32_t *out_node,             /* DEVICE [item_cap] or NULL                    */
+                      uint64_t *out_energy,           /* DEVICE [item_cap * Z] or NULL                */
+                      double   *out_power,            /* DEVICE [item_cap * Z] or NULL                */
+                      void *stream);
 
 /* Algorithmic HBM bytes of K consecutive intervals of these sizes: K times
  * kacc_interval_bytes, or (carried != 0: kacc_run_intervals' one-launch path,

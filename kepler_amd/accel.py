@@ -107,6 +107,7 @@ EXPORTS = [
     "kacc_format_lines_dev",
     "kacc_top_nodes",
     "kacc_top_fleet",
+    "kacc_select_above",
     "kacc_zone_agg_create",
     "kacc_zone_agg_destroy",
     "kacc_zone_agg_read",
@@ -350,6 +351,8 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.kacc_unpack.argtypes = [c_void_p, c_int, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.kacc_top_nodes.argtypes = [c_void_p, c_int, c_uint32, c_uint32, POINTER(KaccTopRows)] + [c_void_p] * 5
     lib.kacc_top_fleet.argtypes = [c_void_p, c_int, c_uint32, c_uint32, POINTER(KaccTopRows)] + [c_void_p] * 6
+    lib.kacc_select_above.argtypes = ([c_void_p, c_int, c_uint32, ctypes.c_uint64, POINTER(KaccTopRows), c_void_p,
+                                       c_uint32] + [c_void_p] * 7)
     lib.kacc_last_error_copy.argtypes = [c_void_p, c_char_p, ctypes.c_size_t]
     lib.kacc_last_error_copy.restype = ctypes.c_size_t
     lib.kacc_create_multi.argtypes = [POINTER(c_int), c_int, POINTER(KaccConfig), POINTER(c_void_p),
@@ -733,6 +736,20 @@ class Accel:
                                             c_void_p(out_count_ptr or None), c_void_p(out_row_ptr or None),
                                             c_void_p(out_slot_ptr or None), c_void_p(out_node_ptr or None),
                                             c_void_p(out_value_ptr or None), c_void_p(stream or None)))
+
+    def select_above(self, table: str, zone: int, threshold_bits: int, rows: KaccTopRows, node_mask_ptr: int,
+                     item_cap: int, node_off_ptr: int, out_row_ptr: int = 0, out_slot_ptr: int = 0,
+                     out_node_ptr: int = 0, out_energy_ptr: int = 0, out_power_ptr: int = 0, stream: int = 0) -> None:
+        """kacc_select_above: the running workloads of the batch whose value of `table` in `zone` is at
+        or above the threshold (µJ, or the bits of the f64 µW), in batch row order: per-node offsets
+        [n_nodes + 1] and dense row / slot / node [item_cap], energy / power [item_cap * Z] (device
+        pointers; item_cap 0 sizes only)."""
+        self._check(self.lib.kacc_select_above(self.ctx, TABLE_INDEX[table], zone, threshold_bits, ctypes.byref(rows),
+                                               c_void_p(node_mask_ptr or None), item_cap,
+                                               c_void_p(node_off_ptr or None), c_void_p(out_row_ptr or None),
+                                               c_void_p(out_slot_ptr or None), c_void_p(out_node_ptr or None),
+                                               c_void_p(out_energy_ptr or None), c_void_p(out_power_ptr or None),
+                                               c_void_p(stream or None)))
 
     def namespace_totals(self, n_ns: int, ns_pod_off_ptr: int, ns_pod_slot_ptr: int,
                          out_energy_ptr: int, out_power_ptr: int, stream: int = 0) -> None:
