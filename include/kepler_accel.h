@@ -46,8 +46,8 @@
 extern "C" {
 #endif
 
-/* Still 6 with kacc_tracker_read, kacc_format_lines_dev and kacc_select_above: they are new symbols
- * only (no struct, no existing signature or result changed), so a client built
+/* Still 6 with kacc_tracker_read, kacc_format_lines_dev, kacc_select_above and
+ * kacc_group_sums: they are new symbols only (no struct, no existing signature or result changed), so a client built
  * against an earlier ABI-6 header runs unchanged.                              */
 #define KACC_ABI_VERSION 6u
 #define KACC_MAX_ZONES 8u
@@ -1070,6 +1070,94 @@ int kacc_select_above(kacc_ctx *ctx, kacc_table t, uint32_t zone, uint64_t thres
                       uint64_t *out_energy,           /* DEVICE [item_cap * Z] or NULL                */
                       double   *out_power,            /* DEVICE [item_cap * Z] or NULL                */
                       void *stream);
+
+/* ---- running workloads summed by group (ABI 6, additive) ---------------------
+ * "Process energy by comm", "container power by runtime", "anything by rack":
+ * PromQL's `sum by (label)` over the RUNNING set, for any workload kind and any
+ * label, computed where the rows are.  The caller maps every row of its last
+ * interval batch to a group id; the call sums the rows' energy and power records
+ * per group.  No reference call is replaced (Kepler exports every row; the sum
+ * is PromQL's).  kacc_namespace_totals is the pods-by-namespace case from a
+ * host-built CSR; this call takes a plain [n_rows] id array.
+ *
+ * ROWS, LISTING AND VALIDITY — kacc_select_above's to the letter.  rows
+ * describes ONE kind's rows of the caller's last interval batch.  A node
+ * contributes nothing when node_mask (DEVICE [n_nodes], nonzero = listed;
+ * NULL = all) unlists it or rows->node_status flags it KACC_NODE_READ_ERROR.
+ * The rows are those of each node's last processed interval, and the call is
+ * ordered after that interval and before the context's next one.  For the
+ * derived kinds (processes, containers, VMs) a node's guard operands
+ * (ActivePower, activeEnergy, ProcessTotalCPUTimeDelta) are read once for the
+ * node that lists the row, not through KACC_T_*_NODE.
+ *
+ * ROW VALUES.  Row r's energy record is the Z words of the kind's energy table
+ * at slot word & KACC_SLOT_MASK, its power record the Z f64 of the kind's power
+ * table there: bit for bit what kacc_table_read returns (derived for processes,
+ * containers and VMs, the stored record for pods).
+ *
+ * CONTRIBUTING ROWS.  A row contributes iff its node is listed and
+ * group[r] < n_groups.  group[r] == KACC_GROUP_NONE leaves the row out
+ * silently.  A listed row with any other id >= n_groups is left out, and so is
+ * a listed row whose slot & KACC_SLOT_MASK is past the kind's capacity, and so
+ * are all rows of a node whose row range is not inside [0, n_rows); each raises
+ * KACC_ERANGE at kacc_sync (bit 8192 of the device error word, "group sums").
+ * Every index is clamped as in kacc_select_above: no input faults, and every
+ * other row's contribution is still exact.
+ *
+ * THE SUMS, for group g and zone z, over the contributing rows of g:
+ *   out_count[g]          the number of rows;
+ *   out_energy[g*Z+z]     the sum of EnergyTotal[z] (µJ) mod 2^64;
+ *   out_power_fx[g*Z+z]   the sum mod 2^64 of fx(p), p the row's power in zone
+ *                         z (µW): a two's-complement i64 in units of 2^-12 µW
+ *                         (KACC_GROUP_POWER_FRAC_BITS).
+ *                           fx(p) = (uint64_t)(int64_t)(p * 4096.0), truncated
+ *                         toward zero, when p is finite and |p| < 2^50 µW (the
+ *                         product is exact: a power of two); otherwise - NaN,
+ *                         ±Inf, |p| >= 2^50 - fx(p) = 0 and the (row, zone)
+ *                         pair is counted in out_dropped[g].  Negative powers
+ *                         occur (a reused PID gives a negative CPU-time delta)
+ *                         and add as negative integers;
+ *   out_power[g*Z+z]      (double)(int64_t)out_power_fx[g*Z+z] * 2^-12: the
+ *                         conversion correctly rounded (nearest even), the
+ *                         scaling exact.  The dense f64 µW array
+ *                         kacc_format_lines_dev takes: a group's sums become
+ *                         sample lines with the caller's group labels;
+ *   out_dropped[g]        the (row, zone) pairs whose power was dropped.
+ * RESOLUTION AND RANGE.  Each row's truncation error is below 2^-12 µW
+ * (0.24 nW), so a group of n rows is within n * 2^-12 µW of the exact sum.  A
+ * group's power must stay below 2^51 µW (about 2.2 GW) for the i64 not to wrap.
+ * Every sum is an integer, so it does not depend on the order of the rows, the
+ * kernel's tiling, a split of the rows into shards or the number of GPUs: two
+ * calls on the same inputs give the same bytes.
+ *
+ * OUTPUTS.  Every non-NULL output is written for every group (zeros for a
+ * group without rows, also with n_rows or n_nodes 0); outputs are overwritten,
+ * never accumulated into.
+ *
+ * CLUSTER USE.  out_energy and out_power_fx of several shards or GPUs add
+ * exactly, word by word mod 2^64, through the u64 vector of
+ * kacc_allreduce_sums; out_power of the total is then the conversion above.
+ *
+ * ERRORS — KACC_EINVAL, nothing launched: a NULL ctx / rows / row_off, a NULL
+ * slot or group with n_rows > 0, an unknown kind, n_groups outside
+ * 1 .. KACC_GROUP_MAX, n_nodes > the context's nodes, all five outputs NULL.
+ *
+ * Asynchronous on `stream` (NULL = the context's): nothing is read back, there
+ * is no device-wide synchronize, and the scratch memory is stream-ordered.    */
+#define KACC_GROUP_NONE 0xffffffffu        /* a row that belongs to no group            */
+#define KACC_GROUP_MAX 65536u              /* largest n_groups                          */
+#define KACC_GROUP_POWER_FRAC_BITS 12u     /* fixed-point power: units of 2^-12 µW      */
+int kacc_group_sums(kacc_ctx *ctx, kacc_kind kind,
+                    const kacc_top_rows *rows,   /* the kind's rows of the last interval batch   */
+                    const uint32_t *group,       /* DEVICE [n_rows] group of each batch row      */
+                    uint32_t n_groups,
+                    const uint32_t *node_mask,   /* DEVICE [n_nodes], nonzero = listed; NULL=all */
+                    uint32_t *out_count,         /* DEVICE [n_groups]      or NULL               */
+                    uint64_t *out_energy,        /* DEVICE [n_groups * Z]  or NULL               */
+                    uint64_t *out_power_fx,      /* DEVICE [n_groups * Z]  or NULL               */
+                    double   *out_power,         /* DEVICE [n_groups * Z]  or NULL               */
+                    uint32_t *out_dropped,       /* DEVICE [n_groups]      or NULL               */
+                    void *stream);
 
 /* Algorithmic HBM bytes of K consecutive intervals of these sizes: K times
  * kacc_interval_bytes, or (carried != 0: kacc_run_intervals' one-launch path,

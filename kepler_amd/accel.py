@@ -54,6 +54,9 @@ KACC_UNIQUE_ID_BYTES = 128
 KACC_PROC_REGULAR, KACC_PROC_CONTAINER, KACC_PROC_VM = 0, 1, 2
 KACC_KEY_TOMB = 0xFFFFFFFFFFFFFFFE
 KACC_TOP_MAX = 1024  # largest k of kacc_top_nodes / kacc_top_fleet
+KACC_GROUP_NONE = 0xFFFFFFFF  # kacc_group_sums: a row that belongs to no group
+KACC_GROUP_MAX = 65536  # largest n_groups
+KACC_GROUP_POWER_FRAC_BITS = 12  # out_power_fx: units of 2^-12 µW
 KACC_TRACKER_READ_CLEAR = 0x1  # kacc_tracker_read: clear the listed nodes' trackers behind the read
 
 # kacc_table enum, in header order: (name, numpy dtype)
@@ -108,6 +111,7 @@ EXPORTS = [
     "kacc_top_nodes",
     "kacc_top_fleet",
     "kacc_select_above",
+    "kacc_group_sums",
     "kacc_zone_agg_create",
     "kacc_zone_agg_destroy",
     "kacc_zone_agg_read",
@@ -353,6 +357,7 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.kacc_top_fleet.argtypes = [c_void_p, c_int, c_uint32, c_uint32, POINTER(KaccTopRows)] + [c_void_p] * 6
     lib.kacc_select_above.argtypes = ([c_void_p, c_int, c_uint32, ctypes.c_uint64, POINTER(KaccTopRows), c_void_p,
                                        c_uint32] + [c_void_p] * 7)
+    lib.kacc_group_sums.argtypes = ([c_void_p, c_int, POINTER(KaccTopRows), c_void_p, c_uint32] + [c_void_p] * 7)
     lib.kacc_last_error_copy.argtypes = [c_void_p, c_char_p, ctypes.c_size_t]
     lib.kacc_last_error_copy.restype = ctypes.c_size_t
     lib.kacc_create_multi.argtypes = [POINTER(c_int), c_int, POINTER(KaccConfig), POINTER(c_void_p),
@@ -750,6 +755,19 @@ class Accel:
                                                c_void_p(out_slot_ptr or None), c_void_p(out_node_ptr or None),
                                                c_void_p(out_energy_ptr or None), c_void_p(out_power_ptr or None),
                                                c_void_p(stream or None)))
+
+    def group_sums(self, kind: int, rows: KaccTopRows, group_ptr: int, n_groups: int, node_mask_ptr: int = 0,
+                   out_count_ptr: int = 0, out_energy_ptr: int = 0, out_power_fx_ptr: int = 0, out_power_ptr: int = 0,
+                   out_dropped_ptr: int = 0, stream: int = 0) -> None:
+        """kacc_group_sums: the running workloads of the batch (KACC_KIND_*) summed by the group id of
+        each row (device u32 [n_rows]; KACC_GROUP_NONE = no group): count and dropped [n_groups],
+        energy (u64 µJ), power_fx (i64 words in 2^-12 µW) and power (f64 µW) [n_groups * Z] (device
+        pointers, each optional)."""
+        self._check(self.lib.kacc_group_sums(self.ctx, kind, ctypes.byref(rows), c_void_p(group_ptr or None), n_groups,
+                                             c_void_p(node_mask_ptr or None), c_void_p(out_count_ptr or None),
+                                             c_void_p(out_energy_ptr or None), c_void_p(out_power_fx_ptr or None),
+                                             c_void_p(out_power_ptr or None), c_void_p(out_dropped_ptr or None),
+                                             c_void_p(stream or None)))
 
     def namespace_totals(self, n_ns: int, ns_pod_off_ptr: int, ns_pod_slot_ptr: int,
                          out_energy_ptr: int, out_power_ptr: int, stream: int = 0) -> None:

@@ -1,0 +1,507 @@
+// Running workloads summed by a caller-defined group, on the device.
+//
+// No reference counterpart: Kepler exports every running workload and leaves `sum by (label)` to
+// PromQL.  Row r of the caller's last interval batch (one workload kind) adds its Z-word energy
+// record and its Z powers, as fixed-point integers of 2^-12 µW, into the sums of group[r].
+// Every sum is an integer mod 2^64, so the order of the additions is free and the result is the
+// same bits for any tiling, any shard split and any number of GPUs.
+//
+//   node_prep   one thread per node: the listed flag and the guard bit of each zone, ONCE per
+//               node (kacc_rows.hpp; kacc_select.hip's)
+//   bin         the groups' bins (count | dropped, Z energies, Z powers) fit in LDS: persistent
+//               workgroups, each walks every splits-th tile of kTile batch rows (the row's node
+//               by search in row_off), gathers every contributing row's record and adds it with
+//               64-bit LDS adds.  A group count small enough is replicated per lane subset, so
+//               the lanes of a wave do not queue on one bin
+//   rows, pass  more groups than LDS holds: `rows` classifies every row ONCE (one workgroup per
+//               tile) into a row word - the group id and the node's guard bits, or "no group" -
+//               and the row's node.  `pass` is a grid of passes x splits persistent workgroups;
+//               a pass owns a range of `bins` groups.  Every workgroup reads the tile's 4-byte row
+//               words; only the workgroup whose pass owns the row's group gathers its record
+//   flush       (the end of bin and pass) a workgroup adds its non-zero bins into the zeroed
+//               accumulator with u64 atomics, consecutive lanes on consecutive words: one atomic
+//               per workgroup and bin word, never one per row
+//   finish      one thread per accumulator word: the outputs, and out_power from out_power_fx
+// Every index is clamped (rows to the batch, slots to slot 0, nodes by the search's range, group
+// ids by the pass's range), so no batch faults.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "kacc_derive.hpp"
+#include "kacc_internal.hpp"
+#include "kacc_rows.hpp"
+
+namespace kacc {
+namespace grp {
+
+constexpr uint32_t kThreads = 256;
+constexpr uint32_t kPer = 8;                      // rows per lane and tile
+constexpr uint32_t kChunk = 4;                    // rows whose records a lane has in flight together
+constexpr uint32_t kTile = kThreads * kPer;       // rows per tile
+constexpr uint32_t kSmallWords = 4096;            // u64 of LDS bins: 32 KiB, three workgroups per CU
+constexpr uint32_t kBigWords = 9984;              // 78 KiB, two workgroups per CU: 1,109 groups at Z = 4
+constexpr uint32_t kPassWords = 9728;             // a pass's bins: 76 KiB, 1,080 groups at Z = 4
+constexpr uint32_t kQueue = 128;                  // a wave's queued rows in a pass (2 KiB per workgroup)
+constexpr uint32_t kPassPer = 16;                 // row words per lane and step of a pass
+constexpr uint32_t kPassTile = kThreads * kPassPer;
+constexpr uint32_t kCus = 256;                    // MI355X
+constexpr uint32_t kMaxCopies = 64;               // one copy of the bins per lane of a wave
+constexpr uint32_t kErrGroup = 1u << 13;          // a group id or a slot past its range, a row range
+                                                  // outside the batch
+constexpr uint64_t kFxLimit = (1023ull + 50ull) << 52;  // the bits of 2^50: |p| at or past it is dropped
+// the row word of the `rows` pass: the group id, the node's guard bits above it
+constexpr uint32_t kWordGroup = 0xffffu, kWordGuardShift = 16;
+static_assert(KACC_GROUP_MAX <= kWordGroup + 1u && KACC_MAX_ZONES <= 8u, "a row word holds the id and the guard bits");
+using rows::kListed;
+using u64x2 = __attribute__((ext_vector_type(2))) unsigned long long;
+
+struct Args {
+  // the kind's records
+  const uint64_t *tab_e, *tab_p;  // the energy table; the stored power (pods) or NULL
+  uint32_t tab_stride;            // Z, or 2Z for the pod records
+  ProcDerive pd;                  // derived power
+  uint32_t Z, derived;
+  uint64_t cap;  // the kind's slot capacity
+  // the rows
+  uint32_t n_nodes, n_rows, tiles;
+  const uint32_t *row_off, *slot, *node_status, *node_mask, *group;
+  uint32_t n_groups;
+  // the grid
+  uint32_t splits;                // workgroups that share the tiles
+  uint32_t copies, copy_stride;   // bin: 2^k copies of the bins, copy_stride u64 apart
+  uint32_t bins, passes;          // pass: groups per pass; workgroup b takes pass b % passes, split b / passes
+  // scratch
+  uint32_t *nflags;  // [n_nodes]
+  uint64_t *acc;     // [n_groups] count | dropped << 32, [n_groups * Z] energy, [n_groups * Z] power_fx
+  uint32_t *row_word, *row_node;  // [n_rows] (pass only)
+  // the outputs
+  uint32_t *out_count, *out_dropped;
+  uint64_t *out_e, *out_fx;
+  double *out_p;
+  uint32_t *err;
+};
+
+// fx(p) of the header for the f64 with these bits; a dropped value counts in `dropped`.
+__device__ __forceinline__ uint64_t power_fx(uint64_t bits, uint32_t &dropped) {
+  const bool keep = (bits & 0x7fffffffffffffffull) < kFxLimit;  // finite and |p| < 2^50
+  dropped += !keep;
+  const double p = __longlong_as_double(static_cast<long long>(keep ? bits : 0ull));
+  return static_cast<uint64_t>(static_cast<long long>(p * 4096.0));  // exact product, truncated toward zero
+}
+__device__ __forceinline__ uint64_t derived_bits(uint32_t f, uint32_t z, double ratio, double aP) {
+  return static_cast<uint64_t>(__double_as_longlong(((f >> z) & 1u) ? ratio * aP : 0.0));
+}
+__device__ __forceinline__ void lds_add(uint64_t *p, uint64_t v) {
+  atomicAdd(reinterpret_cast<unsigned long long *>(p), static_cast<unsigned long long>(v));
+}
+
+__global__ __launch_bounds__(kThreads) void node_prep_kernel(const Args a) {
+  const uint32_t n = blockIdx.x * kThreads + threadIdx.x;
+  if (n >= a.n_nodes) return;
+  bool bad_range;
+  const uint32_t f = rows::node_flags(a.row_off, a.node_status, a.node_mask, a.pd, a.derived, a.Z, a.n_rows, n, bad_range);
+  if (bad_range) atomicOr(a.err, kErrGroup);  // left out
+  a.nflags[n] = f;
+}
+
+struct TileRows {  // a lane's kPer rows of a tile
+  bool in_batch[kPer], ok[kPer];  // ok: the row contributes
+  uint32_t r[kPer], sl[kPer], g[kPer], node[kPer], f[kPer];  // the slot is clamped to slot 0
+};
+// Classifies the tile's rows; true when a listed row of this lane has a slot or a group id out
+// of range.  No load sits behind a branch: a row past the batch is clamped to its last row.
+__device__ __forceinline__ bool classify_tile(const Args &a, uint32_t tile, uint32_t lane, uint32_t wave, TileRows &t) {
+  const rows::TileNodes tn = rows::tile_nodes(a.row_off, a.n_nodes, a.n_rows, tile, kTile, lane);
+  const uint64_t row0 = static_cast<uint64_t>(tile) * kTile + wave * (kPer * 64u) + lane;
+  const uint32_t last_row = a.n_rows - 1;
+  uint32_t w[kPer], hi[kPer];
+#pragma unroll
+  for (uint32_t u = 0; u < kPer; ++u) {
+    const uint64_t rr = row0 + u * 64u;
+    t.in_batch[u] = rr <= last_row;
+    t.r[u] = static_cast<uint32_t>(min(rr, static_cast<uint64_t>(last_row)));
+    w[u] = a.slot[t.r[u]];
+    t.g[u] = a.group[t.r[u]];
+    t.node[u] = tn.first;
+    hi[u] = tn.last;
+  }
+  for (uint32_t s = 0; s < tn.steps; ++s) {  // workgroup-uniform
+#pragma unroll
+    for (uint32_t u = 0; u < kPer; ++u) rows::node_step(a.row_off, t.r[u], t.node[u], hi[u]);
+  }
+  bool bad = false;
+#pragma unroll
+  for (uint32_t u = 0; u < kPer; ++u) {
+    const uint32_t n = t.node[u];
+    const uint32_t r0 = a.row_off[n], r1 = a.row_off[n + 1];
+    t.f[u] = a.nflags[n];
+    const bool listed = t.in_batch[u] && r0 <= t.r[u] && t.r[u] < r1 && (t.f[u] & kListed);
+    const uint32_t s = w[u] & KACC_SLOT_MASK;
+    const bool in = s < a.cap, gin = t.g[u] < a.n_groups;
+    bad = bad || (listed && (!in || (!gin && t.g[u] != KACC_GROUP_NONE)));  // left out
+    t.ok[u] = listed && in && gin;
+    t.sl[u] = in ? s : 0u;
+  }
+  return bad;
+}
+
+// Adds one row's record (slot sl below the capacity, its node, the node's guard bits f) into bin
+// `bin` of b_cd / b_e / b_p.  kZ: the zone count when it is 4 (16-byte loads), else 0: any Z.
+template <uint32_t kZ>
+__device__ __forceinline__ void add_one(const Args &a, uint32_t sl, uint32_t node, uint32_t f, uint32_t bin,
+                                        uint64_t *b_cd, uint64_t *b_e, uint64_t *b_p) {
+  const uint32_t Z = kZ ? kZ : a.Z;
+  const uint64_t *se = a.tab_e + static_cast<uint64_t>(sl) * a.tab_stride;
+  const uint64_t *sp = a.derived ? reinterpret_cast<const uint64_t *>(a.pd.active_power) + static_cast<uint64_t>(node) * Z
+                                 : a.tab_p + static_cast<uint64_t>(sl) * a.tab_stride;
+  const double ratio = a.derived ? a.pd.ratio[sl] : 0.0;
+  uint32_t dropped = 0;
+  if constexpr (kZ == 4) {
+    const u64x2 e0 = reinterpret_cast<const u64x2 *>(se)[0], e1 = reinterpret_cast<const u64x2 *>(se)[1];
+    const u64x2 p0 = reinterpret_cast<const u64x2 *>(sp)[0], p1 = reinterpret_cast<const u64x2 *>(sp)[1];
+    const uint64_t ew[4] = {e0.x, e0.y, e1.x, e1.y}, pw[4] = {p0.x, p0.y, p1.x, p1.y};
+#pragma unroll
+    for (uint32_t z = 0; z < 4; ++z) {
+      const uint64_t bits =
+          a.derived ? derived_bits(f, z, ratio, __longlong_as_double(static_cast<long long>(pw[z]))) : pw[z];
+      lds_add(&b_e[bin * 4u + z], ew[z]);
+      lds_add(&b_p[bin * 4u + z], power_fx(bits, dropped));
+    }
+  } else {
+    for (uint32_t z = 0; z < Z; ++z) {
+      const uint64_t pw = sp[z];
+      const uint64_t bits = a.derived ? derived_bits(f, z, ratio, __longlong_as_double(static_cast<long long>(pw))) : pw;
+      lds_add(&b_e[bin * Z + z], se[z]);
+      lds_add(&b_p[bin * Z + z], power_fx(bits, dropped));
+    }
+  }
+  lds_add(&b_cd[bin], 1ull | static_cast<uint64_t>(dropped) << 32);
+}
+
+// Adds the records of the rows that are `mine` into the bins b_cd / b_e / b_p of nloc groups.
+// kZ: the zone count when it is 4 (a lane keeps kChunk rows' records in registers, 16-byte
+// loads; every row's record is loaded, the slots are clamped, so no load sits behind a
+// data-dependent branch), else 0: any Z, word by word.
+template <uint32_t kZ>
+__device__ __forceinline__ void add_rows(const Args &a, const bool (&mine)[kPer], const uint32_t (&sl)[kPer],
+                                         const uint32_t (&node)[kPer], const uint32_t (&f)[kPer],
+                                         const uint32_t (&bin)[kPer], uint64_t *b_cd, uint64_t *b_e, uint64_t *b_p) {
+  if constexpr (kZ == 4) {
+#pragma unroll
+    for (uint32_t c = 0; c < kPer; c += kChunk) {
+      u64x2 e[kChunk][2], p[kChunk][2];
+      double ratio[kChunk];
+#pragma unroll
+      for (uint32_t j = 0; j < kChunk; ++j) {
+        const uint32_t u = c + j;
+        e[j][0] = e[j][1] = p[j][0] = p[j][1] = u64x2{0ull, 0ull};
+        ratio[j] = 0.0;
+        if (a.cap != 0) {  // uniform
+          const u64x2 *se = reinterpret_cast<const u64x2 *>(a.tab_e + static_cast<uint64_t>(sl[u]) * a.tab_stride);
+          e[j][0] = se[0];
+          e[j][1] = se[1];
+          const u64x2 *sp;
+          if (a.derived) {  // uniform
+            ratio[j] = a.pd.ratio[sl[u]];
+            sp = reinterpret_cast<const u64x2 *>(a.pd.active_power + static_cast<uint64_t>(node[u]) * 4u);
+          } else {
+            sp = reinterpret_cast<const u64x2 *>(a.tab_p + static_cast<uint64_t>(sl[u]) * a.tab_stride);
+          }
+          p[j][0] = sp[0];
+          p[j][1] = sp[1];
+        }
+      }
+#pragma unroll
+      for (uint32_t j = 0; j < kChunk; ++j) {
+        const uint32_t u = c + j;
+        if (!mine[u]) continue;
+        const uint64_t ew[4] = {e[j][0].x, e[j][0].y, e[j][1].x, e[j][1].y};
+        const uint64_t pw[4] = {p[j][0].x, p[j][0].y, p[j][1].x, p[j][1].y};
+        uint32_t dropped = 0;
+#pragma unroll
+        for (uint32_t z = 0; z < 4; ++z) {
+          const uint64_t bits =
+              a.derived ? derived_bits(f[u], z, ratio[j], __longlong_as_double(static_cast<long long>(pw[z]))) : pw[z];
+          lds_add(&b_e[bin[u] * 4u + z], ew[z]);
+          lds_add(&b_p[bin[u] * 4u + z], power_fx(bits, dropped));
+        }
+        lds_add(&b_cd[bin[u]], 1ull | static_cast<uint64_t>(dropped) << 32);
+      }
+    }
+  } else {
+#pragma unroll
+    for (uint32_t u = 0; u < kPer; ++u)
+      if (mine[u]) add_one<0>(a, sl[u], node[u], f[u], bin[u], b_cd, b_e, b_p);
+  }
+}
+
+// The flush: word i of the workgroup's bins of groups [g0, g0 + nloc) (the copies summed) into
+// the accumulator's planes, consecutive lanes on consecutive words.
+__device__ __forceinline__ void flush_bins(const Args &a, const uint64_t *s_bin, uint32_t copies, uint32_t g0,
+                                           uint32_t nloc, uint32_t tid) {
+  const uint32_t Z = a.Z, n_e = nloc * Z;
+  for (uint32_t i = tid; i < nloc + 2u * n_e; i += kThreads) {
+    uint64_t v = 0;
+    for (uint32_t c = 0; c < copies; ++c) v += s_bin[c * a.copy_stride + i];
+    if (v == 0) continue;
+    uint64_t *dst;
+    if (i < nloc)
+      dst = a.acc + g0 + i;
+    else if (i < nloc + n_e)
+      dst = a.acc + a.n_groups + static_cast<uint64_t>(g0) * Z + (i - nloc);
+    else
+      dst = a.acc + a.n_groups + static_cast<uint64_t>(a.n_groups) * Z + static_cast<uint64_t>(g0) * Z + (i - nloc - n_e);
+    atomicAdd(reinterpret_cast<unsigned long long *>(dst), static_cast<unsigned long long>(v));
+  }
+}
+
+// Every group's bins in LDS, `copies` times.
+template <uint32_t kZ, uint32_t kLds>
+__global__ __launch_bounds__(kThreads, kLds == kSmallWords ? 3 : 2) void bin_kernel(const Args a) {
+  __shared__ uint64_t s_bin[kLds];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint32_t Z = kZ ? kZ : a.Z, G = a.n_groups;
+  for (uint32_t i = tid; i < a.copies * a.copy_stride; i += kThreads) s_bin[i] = 0;  // <= kLds (host)
+  __syncthreads();
+  uint64_t *const b_cd = s_bin + (lane & (a.copies - 1u)) * a.copy_stride;
+  uint64_t *const b_e = b_cd + G, *const b_p = b_e + G * Z;
+  bool bad = false;
+  for (uint32_t tile = blockIdx.x; tile < a.tiles; tile += a.splits) {  // workgroup-uniform
+    TileRows t;
+    bad = classify_tile(a, tile, lane, wave, t) || bad;
+    add_rows<kZ>(a, t.ok, t.sl, t.node, t.f, t.g, b_cd, b_e, b_p);
+  }
+  if (bad) atomicOr(a.err, kErrGroup);
+  __syncthreads();
+  flush_bins(a, s_bin, a.copies, 0u, G, tid);
+}
+
+// One workgroup per tile: the row word (group id | guard bits << 16, or KACC_GROUP_NONE for a
+// row that does not contribute) and the node of every row of the batch.
+__global__ __launch_bounds__(kThreads) void rows_kernel(const Args a) {
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  TileRows t;
+  if (classify_tile(a, blockIdx.x, lane, wave, t)) atomicOr(a.err, kErrGroup);
+#pragma unroll
+  for (uint32_t u = 0; u < kPer; ++u) {
+    if (!t.in_batch[u]) continue;
+    a.row_word[t.r[u]] = t.ok[u] ? t.g[u] | (t.f[u] & ((1u << KACC_MAX_ZONES) - 1u)) << kWordGuardShift : KACC_GROUP_NONE;
+    a.row_node[t.r[u]] = t.node[u];
+  }
+}
+
+__device__ __forceinline__ void wave_lds_fence() {  // a wave's LDS writes before its reads (kacc_select.hip's)
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// A pass's range of groups in LDS; the rows by their row words.  About one row word in `passes`
+// is the pass's, so a wave first queues its rows (ballot and popcount, in LDS) and gathers 64
+// queued rows at a time, one per lane: the records' loads of 64 rows are in flight together.
+template <uint32_t kZ>
+__global__ __launch_bounds__(kThreads, 2) void pass_kernel(const Args a) {
+  __shared__ uint64_t s_bin[kPassWords];
+  __shared__ uint32_t s_q[kThreads / 64][kQueue];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint32_t Z = kZ ? kZ : a.Z;
+  const uint32_t pass = blockIdx.x % a.passes, split = blockIdx.x / a.passes;
+  const uint32_t g0 = pass * a.bins;  // < n_groups
+  const uint32_t nloc = min(a.bins, a.n_groups - g0);
+  for (uint32_t i = tid; i < nloc * (1u + 2u * Z); i += kThreads) s_bin[i] = 0;  // <= kPassWords (host)
+  __syncthreads();
+  uint64_t *const b_cd = s_bin, *const b_e = b_cd + nloc, *const b_p = b_e + nloc * Z;
+  uint32_t *const q = s_q[wave];
+  const uint32_t last_row = a.n_rows - 1;
+  const uint32_t pass_tiles = static_cast<uint32_t>((static_cast<uint64_t>(a.n_rows) + kPassTile - 1) / kPassTile);
+
+  // the queued rows q[0 .. n) of this wave, n <= 64, one per lane
+  auto drain = [&](uint32_t n) {
+    if (lane >= n) return;
+    const uint32_t r = min(q[lane], last_row);
+    const uint32_t word = a.row_word[r];
+    const uint32_t bin = min((word & kWordGroup) - g0, nloc - 1u);  // the pass's: checked when it was queued
+    const uint32_t s = a.slot[r] & KACC_SLOT_MASK;
+    const uint32_t sl = s < a.cap ? s : 0u;  // below the capacity when the row word was written
+    const uint32_t node = min(a.row_node[r], a.n_nodes - 1u);
+    add_one<kZ>(a, sl, node, word >> kWordGuardShift, bin, b_cd, b_e, b_p);
+  };
+
+  uint32_t qn = 0;  // wave-uniform: the queued rows, < 64 between steps
+  for (uint32_t tile = split; tile < pass_tiles; tile += a.splits) {  // workgroup-uniform
+    const uint64_t row0 = static_cast<uint64_t>(tile) * kPassTile + wave * (kPassPer * 64u) + lane;
+    uint32_t word[kPassPer];
+#pragma unroll
+    for (uint32_t u = 0; u < kPassPer; ++u)  // a row past the batch is clamped to its last row
+      word[u] = a.row_word[static_cast<uint32_t>(min(row0 + u * 64u, static_cast<uint64_t>(last_row)))];
+#pragma unroll
+    for (uint32_t u = 0; u < kPassPer; ++u) {
+      const uint64_t rr = row0 + u * 64u;
+      const bool mine = rr <= last_row && word[u] != KACC_GROUP_NONE && (word[u] & kWordGroup) - g0 < nloc;
+      const uint64_t m = __ballot(mine);
+      if (m == 0) continue;  // wave-uniform
+      if (mine) q[qn + static_cast<uint32_t>(__popcll(m & ((1ull << lane) - 1ull)))] = static_cast<uint32_t>(rr);
+      qn += static_cast<uint32_t>(__popcll(m));  // <= 127 < kQueue
+      if (qn >= 64u) {
+        wave_lds_fence();
+        drain(64u);
+        const uint32_t rest = qn - 64u;  // < 64
+        const uint32_t moved = q[64u + min(lane, 63u)];
+        wave_lds_fence();
+        if (lane < rest) q[lane] = moved;
+        qn = rest;
+      }
+    }
+  }
+  wave_lds_fence();
+  drain(qn);
+  __syncthreads();
+  flush_bins(a, s_bin, 1u, g0, nloc, tid);
+}
+
+// Every non-NULL output of every group out of the accumulator; out_power is the i64 sum,
+// correctly rounded to f64, times 2^-12 (exact).
+__global__ __launch_bounds__(kThreads) void finish_kernel(const Args a) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kThreads + threadIdx.x;
+  const uint64_t G = a.n_groups, GZ = G * a.Z;
+  if (i < G) {
+    const uint64_t cd = a.acc[i];
+    if (a.out_count) a.out_count[i] = static_cast<uint32_t>(cd);
+    if (a.out_dropped) a.out_dropped[i] = static_cast<uint32_t>(cd >> 32);
+  }
+  if (i < GZ) {
+    const uint64_t fx = a.acc[G + GZ + i];
+    if (a.out_e) a.out_e[i] = a.acc[G + i];
+    if (a.out_fx) a.out_fx[i] = fx;
+    if (a.out_p) a.out_p[i] = static_cast<double>(static_cast<long long>(fx)) * 0x1p-12;
+  }
+}
+
+}  // namespace grp
+}  // namespace kacc
+
+extern "C" {
+
+int kacc_group_sums(kacc_ctx *ctx, kacc_kind kind, const kacc_top_rows *rows, const uint32_t *group, uint32_t n_groups,
+                    const uint32_t *node_mask, uint32_t *out_count, uint64_t *out_energy, uint64_t *out_power_fx,
+                    double *out_power, uint32_t *out_dropped, void *stream) {
+  using namespace kacc::grp;
+  const char *fn = "kacc_group_sums";
+  if (!ctx) return KACC_EINVAL;
+  if (kind != KACC_KIND_PROC && kind != KACC_KIND_CTR && kind != KACC_KIND_VM && kind != KACC_KIND_POD)
+    return kacc_fail(ctx, KACC_EINVAL, "%s: unknown kind %d", fn, (int)kind);
+  if (!rows) return kacc_fail(ctx, KACC_EINVAL, "%s: NULL argument", fn);
+  if (n_groups < 1 || n_groups > KACC_GROUP_MAX)
+    return kacc_fail(ctx, KACC_EINVAL, "%s: n_groups %u outside 1 .. %u", fn, n_groups, KACC_GROUP_MAX);
+  if (rows->n_nodes > ctx->cfg.nodes)
+    return kacc_fail(ctx, KACC_EINVAL, "%s: n_nodes %u > the context's %llu nodes", fn, rows->n_nodes,
+                     (unsigned long long)ctx->cfg.nodes);
+  if (!rows->row_off || (rows->n_rows && (!rows->slot || !group)))
+    return kacc_fail(ctx, KACC_EINVAL, "%s: NULL row array", fn);
+  if (!out_count && !out_energy && !out_power_fx && !out_power && !out_dropped)
+    return kacc_fail(ctx, KACC_EINVAL, "%s: no output array", fn);
+  KACC_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  kacc::TimingScope timing(ctx);
+
+  Args a{};
+  const uint32_t Z = ctx->cfg.zones, W = 1u + 2u * Z;
+  const bool pod = kind == KACC_KIND_POD;
+  const int te = pod ? KACC_T_POD_ENERGY : kind == KACC_KIND_PROC ? KACC_T_PROC_ENERGY
+                 : kind == KACC_KIND_CTR ? KACC_T_CTR_ENERGY : KACC_T_VM_ENERGY;
+  a.cap = kind == KACC_KIND_PROC ? ctx->cfg.proc_slots
+          : kind == KACC_KIND_CTR ? ctx->cfg.ctr_slots
+          : kind == KACC_KIND_VM ? ctx->cfg.vm_slots
+                                 : ctx->cfg.pod_slots;
+  a.pd = kacc_derive(ctx, pod ? KACC_KIND_PROC : kind);
+  a.derived = !pod;
+  a.tab_stride = pod ? 2 * Z : Z;
+  a.tab_e = static_cast<const uint64_t *>(ctx->tables[te]);
+  a.tab_p = pod ? static_cast<const uint64_t *>(ctx->tables[KACC_T_POD_POWER]) : nullptr;  // Z words into the record
+  a.Z = Z;
+  a.n_nodes = rows->n_nodes;
+  a.n_rows = rows->n_rows;
+  // without a node no row is listed
+  a.tiles = a.n_nodes ? static_cast<uint32_t>((static_cast<uint64_t>(a.n_rows) + kTile - 1) / kTile) : 0u;
+  a.row_off = rows->row_off;
+  a.slot = rows->slot;
+  a.node_status = rows->node_status;
+  a.node_mask = node_mask;
+  a.group = group;
+  a.n_groups = n_groups;
+  a.out_count = out_count;
+  a.out_dropped = out_dropped;
+  a.out_e = out_energy;
+  a.out_fx = out_power_fx;
+  a.out_p = out_power;
+  a.err = ctx->d_err;
+
+  // the grid: replicated bins while they fit the small LDS size, else one copy in the large
+  // one, else passes over group ranges
+  const uint32_t stride = (n_groups * W) | 1u;  // odd: the copies of a bin fall into different banks
+  uint32_t lds = kBigWords;
+  a.copies = 1;
+  a.copy_stride = n_groups * W;
+  a.passes = 1;
+  a.bins = n_groups;
+  if (stride <= kSmallWords) {
+    lds = kSmallWords;
+    a.copy_stride = stride;
+    while (a.copies < kMaxCopies && 2 * a.copies * stride <= kSmallWords) a.copies *= 2;
+  } else if (n_groups * W > kBigWords) {
+    a.bins = kPassWords / W;
+    a.passes = (n_groups + a.bins - 1) / a.bins;
+    a.copy_stride = 0;
+  }
+  const uint32_t wgs = kCus * (lds == kSmallWords ? 3u : 2u);
+  const uint32_t pass_tiles = static_cast<uint32_t>((static_cast<uint64_t>(a.n_rows) + kPassTile - 1) / kPassTile);
+  a.splits = std::max(1u, a.passes > 1 ? std::min(pass_tiles, wgs / a.passes) : std::min(a.tiles, wgs));
+
+  // temporaries, stream ordered: the accumulator, the node flags and, for passes, the row words
+  // and nodes
+  const uint64_t acc_words = static_cast<uint64_t>(n_groups) * W;
+  const uint64_t row_words = a.passes > 1 && a.tiles ? a.n_rows : 0;
+  uint64_t *tmp = nullptr;
+  KACC_HIP(ctx, hipMallocAsync(reinterpret_cast<void **>(&tmp), 8 * acc_words + 4ull * a.n_nodes + 8 * row_words, st));
+  a.acc = tmp;
+  a.nflags = reinterpret_cast<uint32_t *>(tmp + acc_words);
+  a.row_word = a.nflags + a.n_nodes;
+  a.row_node = a.row_word + row_words;
+  int rc = KACC_OK;
+  if (hipMemsetAsync(a.acc, 0, 8 * acc_words, st) != hipSuccess) rc = kacc_fail(ctx, KACC_EHIP, "%s: memset", fn);
+
+  if (rc == KACC_OK) {
+    (void)hipGetLastError();  // clear a stale error of an earlier call
+    const dim3 block(kThreads);
+    if (a.n_nodes) KACC_LAUNCH(node_prep_kernel, dim3((a.n_nodes + kThreads - 1) / kThreads), block, 0, st, a);
+    if (a.tiles) {
+      const bool z4 = Z == 4;
+      if (a.passes > 1) {
+        KACC_LAUNCH(rows_kernel, dim3(a.tiles), block, 0, st, a);
+        const dim3 grid(a.passes * a.splits);
+        if (z4)
+          KACC_LAUNCH(pass_kernel<4>, grid, block, 0, st, a);
+        else
+          KACC_LAUNCH(pass_kernel<0>, grid, block, 0, st, a);
+      } else if (lds == kSmallWords) {
+        if (z4)
+          KACC_LAUNCH((bin_kernel<4, kSmallWords>), dim3(a.splits), block, 0, st, a);
+        else
+          KACC_LAUNCH((bin_kernel<0, kSmallWords>), dim3(a.splits), block, 0, st, a);
+      } else {
+        if (z4)
+          KACC_LAUNCH((bin_kernel<4, kBigWords>), dim3(a.splits), block, 0, st, a);
+        else
+          KACC_LAUNCH((bin_kernel<0, kBigWords>), dim3(a.splits), block, 0, st, a);
+      }
+    }
+    const uint64_t words = static_cast<uint64_t>(n_groups) * Z;
+    KACC_LAUNCH(finish_kernel, dim3(static_cast<uint32_t>((words + kThreads - 1) / kThreads)), block, 0, st, a);
+    if (hipGetLastError() != hipSuccess) rc = kacc_fail(ctx, KACC_EHIP, "%s: launch", fn);
+  }
+  (void)hipFreeAsync(tmp, st);
+  return rc;
+}
+
+}  // extern "C"

@@ -30,6 +30,7 @@
 
 #include "kacc_derive.hpp"
 #include "kacc_internal.hpp"
+#include "kacc_rows.hpp"
 
 namespace kacc {
 namespace sel {
@@ -40,8 +41,7 @@ constexpr uint32_t kWords = kWaves * kPer;     // mask words per tile (<= 64: on
 constexpr uint32_t kTile = kWords * 64;        // rows per tile
 constexpr uint32_t kErrSelect = 1u << 12;      // more items than item_cap, a slot past the capacity,
                                                // a row range outside the batch
-constexpr uint32_t kListed = 1u << 31;         // node flag word: bit z = zone z passed the guard
-static_assert(KACC_MAX_ZONES < 31, "the zones' guard bits and kListed share a word");
+using rows::kListed;                           // node flag word: bit z = zone z passed the guard
 
 enum Src { kEnergy = 0, kStored = 1, kDerived = 2 };  // the table of the predicate
 
@@ -84,64 +84,17 @@ __global__ __launch_bounds__(kThreads) void node_prep_kernel(const Args a) {
   const uint32_t n = blockIdx.x * kThreads + threadIdx.x;
   if (n == 0) a.cnt[a.tiles] = 0;
   if (n >= a.n_nodes) return;
-  const uint32_t r0 = a.row_off[n], r1 = a.row_off[n + 1];
-  const uint32_t status = a.node_status ? a.node_status[n] : 0u;
-  const uint32_t listed = a.node_mask ? a.node_mask[n] : 1u;
-  uint32_t f = 0;
-  if (a.derived) {  // uniform; the guard (process.go:124), once per node and zone
-    const double cd = a.pd.cpu_delta[n];
-    for (uint32_t z = 0; z < a.Z; ++z) {
-      const uint64_t i = static_cast<uint64_t>(n) * a.Z + z;
-      const bool live = !(a.pd.active_energy[i] == 0 || !(cd != 0) || !(a.pd.active_power[i] != 0));
-      f |= static_cast<uint32_t>(live) << z;
-    }
-  }
-  if (r0 > r1 || r1 > a.n_rows)
-    atomicOr(a.err, kErrSelect);  // left out
-  else if (listed && !(status & KACC_NODE_READ_ERROR))
-    f |= kListed;
+  bool bad_range;
+  const uint32_t f = rows::node_flags(a.row_off, a.node_status, a.node_mask, a.pd, a.derived, a.Z, a.n_rows, n, bad_range);
+  if (bad_range) atomicOr(a.err, kErrSelect);  // left out
   a.nflags[n] = f;
 }
 
-// One round of a wave-wide 64-ary search for the smallest n in [lo, hi] with off[n + 1] > x
-// (kacc_tracker.hip's, over the u32 row offsets): one round trip, the range shrinks 64-fold.
-__device__ __forceinline__ void node_search_round(const uint32_t *off, uint32_t x, uint32_t lane, uint32_t &lo,
-                                                  uint32_t &hi) {
-  const uint64_t st = (hi - lo) / 64u + 1u;
-  const uint64_t q = min(lo + lane * st + (st - 1), static_cast<uint64_t>(hi));
-  const uint64_t m = __ballot(off[q + 1] > x);
-  const uint64_t b = lo + (m ? static_cast<uint32_t>(__builtin_ctzll(m)) : 63u) * st;
-  const uint32_t nlo = static_cast<uint32_t>(min(b, static_cast<uint64_t>(hi)));
-  const uint32_t nhi = static_cast<uint32_t>(min(b + (st - 1), static_cast<uint64_t>(hi)));
-  lo = __builtin_amdgcn_readfirstlane(nlo);
-  hi = __builtin_amdgcn_readfirstlane(nhi);
-}
-
-struct TileNodes {  // the nodes of the tile's first and last row, and the steps between them
-  uint32_t first, last, steps;
-};
+// The tile-to-node search (kacc_rows.hpp) over this call's rows.
+using rows::node_step;
+using rows::TileNodes;
 __device__ __forceinline__ TileNodes tile_nodes(const Args &a, uint32_t tile, uint32_t lane) {
-  const uint32_t x0 = tile * kTile;  // < n_rows
-  const uint32_t x1 = static_cast<uint32_t>(min(static_cast<uint64_t>(x0) + kTile, static_cast<uint64_t>(a.n_rows)) - 1);
-  uint32_t la = 0, ha = a.n_nodes - 1, lb = 0, hb = a.n_nodes - 1;
-  while (ha > la || hb > lb) {  // the two searches' loads share a round trip
-    node_search_round(a.row_off, x0, lane, la, ha);
-    node_search_round(a.row_off, x1, lane, lb, hb);
-  }
-  TileNodes t;
-  t.first = la;
-  t.last = max(la, lb);
-  const uint32_t span = t.last - t.first;
-  t.steps = span ? 32u - static_cast<uint32_t>(__builtin_clz(span)) : 0u;  // ceil(log2(span + 1))
-  return t;
-}
-// One step of a lane's own search between the tile's nodes: the smallest n with
-// row_off[n + 1] > r (empty nodes are stepped over).  The load is unconditional.
-__device__ __forceinline__ void node_step(const uint32_t *row_off, uint32_t r, uint32_t &lo, uint32_t &hi) {
-  const uint32_t mid = (lo + hi) >> 1;
-  const bool up = row_off[mid + 1] > r, open = lo < hi;
-  hi = (open && up) ? mid : hi;
-  lo = (open && !up) ? mid + 1 : lo;
+  return rows::tile_nodes(a.row_off, a.n_nodes, a.n_rows, tile, kTile, lane);
 }
 
 template <int kSrc>
