@@ -46,8 +46,8 @@
 extern "C" {
 #endif
 
-/* Still 6 with kacc_tracker_read, kacc_format_lines_dev, kacc_select_above and
- * kacc_group_sums: they are new symbols only (no struct, no existing signature or result changed), so a client built
+/* Still 6 with kacc_tracker_read, kacc_format_lines_dev, kacc_select_above,
+ * kacc_group_sums and kacc_group_hist: they are new symbols only (no struct, no existing signature or result changed), so a client built
  * against an earlier ABI-6 header runs unchanged.                              */
 #define KACC_ABI_VERSION 6u
 #define KACC_MAX_ZONES 8u
@@ -1157,6 +1157,100 @@ int kacc_group_sums(kacc_ctx *ctx, kacc_kind kind,
                     uint64_t *out_power_fx,      /* DEVICE [n_groups * Z]  or NULL               */
                     double   *out_power,         /* DEVICE [n_groups * Z]  or NULL               */
                     uint32_t *out_dropped,       /* DEVICE [n_groups]      or NULL               */
+                    void *stream);
+
+/* ---- value histograms of the running workloads by group (ABI 6, additive) ----
+ * "How many processes draw under 1 mW, under 10 mW, under 1 W, per rack", "the
+ * p99 of container power per runtime": a Prometheus histogram (_bucket{le=..},
+ * _sum, _count) of ONE value per row over the RUNNING set, per caller-defined
+ * group, computed where the rows are.  No reference call is replaced (Kepler
+ * exports every row; the histogram is the consumer's).
+ *
+ * TABLE, ZONE, ROWS, LISTING AND VALIDITY — kacc_select_above's to the letter.
+ * t is one of the eight workload tables KACC_T_{PROC,CTR,VM,POD}_{ENERGY,POWER}
+ * (the table implies the kind), zone < Z, and value(r) is the element of t at
+ * (row r's slot word & KACC_SLOT_MASK, zone), bit for bit what kacc_table_read
+ * returns: for processes, containers and VMs the derived power (the node's guard
+ * operands are read once for the node that lists the row, the product has no
+ * FMA, and the value is 0.0 when the zone's guard fails), for pods the stored
+ * record.  A node contributes nothing when node_mask (DEVICE [n_nodes], nonzero
+ * = listed; NULL = all) unlists it, when rows->node_status flags it
+ * KACC_NODE_READ_ERROR, or when its row range is not inside [0, n_rows).  The
+ * rows are those of each node's last processed interval, and the call is
+ * ordered after that interval and before the context's next one.
+ *
+ * GROUP IDS — kacc_group_sums'.  A row contributes iff its node is listed, its
+ * slot & KACC_SLOT_MASK is below the kind's capacity and group[r] < n_groups.
+ * group[r] == KACC_GROUP_NONE leaves the row out silently.  Any other id
+ * >= n_groups, a slot past the capacity, or a node's row range outside the
+ * batch leaves those rows out, and each raises KACC_ERANGE at kacc_sync (bit
+ * 16384 of the device error word, "histogram").  group == NULL requires
+ * n_groups == 1: every listed row is then in group 0 (the fleet histogram).
+ *
+ * BOUNDS.  bounds holds the same kind of bits as kacc_select_above's threshold:
+ * µJ for an energy table, the bits of an f64 µW for a power table.  It is a
+ * HOST array and is read before the call returns: the caller may free it at
+ * once.  With key() the u64 sort key of the top lists (an energy is its own
+ * key; a power: NaN -> 0, ±0 -> 1<<63, p > 0 -> bits | 1<<63, p < 0 -> ~bits),
+ * key(bounds[j]) must be strictly ascending, and a NaN bound is invalid for a
+ * power table.
+ *
+ * BINS.  A contributing row whose power is a NaN is in no bin: it adds 1 to
+ * out_nan[g] and nothing else (an energy table has no NaN).  Every other
+ * contributing row falls in bin j = the number of bounds i with
+ * key(bounds[i]) < key(value).  Consequences:
+ *   - bin 0 is value <= bounds[0];
+ *   - bin j is bounds[j-1] < value <= bounds[j];
+ *   - bin n_bounds is "above the last bound" (Prometheus's +Inf);
+ *   - -0.0 and +0.0 share a key: a bound of either includes both.
+ *
+ * OUTPUTS, for group g, with B1 = n_bounds + 1:
+ *   out_bin[g*B1 + j]   the rows of bin j;
+ *   out_cum[g*B1 + j]   the sum of bins 0 .. j (_bucket{le=bounds[j]});
+ *                       out_cum[g*B1 + n_bounds] is _count, the binned rows;
+ *   out_sum[g]          _sum over the binned rows: for an energy table the sum
+ *                       of the values mod 2^64; for a power table the sum mod
+ *                       2^64 of kacc_group_sums' fx(p) (a two's-complement i64
+ *                       in units of 2^-12 µW, truncated toward zero).  ±Inf
+ *                       and |p| >= 2^50 µW are binned but add 0 to the sum;
+ *   out_nan[g]          contributing rows whose power is a NaN;
+ *   out_unsummed[g]     binned rows whose power is ±Inf or |p| >= 2^50 µW (the
+ *                       ones out_sum[g] does not hold).
+ * Every non-NULL output is written for every group (zeros for a group without
+ * rows, also with n_rows or n_nodes 0); outputs are overwritten, never
+ * accumulated into.  Every word is an integer, so it does not depend on the
+ * order of the rows, the kernel's tiling, a split of the rows into shards or
+ * the number of GPUs: two calls on the same inputs give the same bytes.
+ *
+ * CLUSTER USE.  All outputs are u64, so out_bin, out_sum, out_nan and
+ * out_unsummed of several shards or GPUs add exactly, word by word, through the
+ * u64 vector of kacc_allreduce_sums; out_cum of the total is the prefix sum of
+ * the added out_bin (the added out_cum is the same words).
+ *
+ * ERRORS — KACC_EINVAL, nothing launched: a NULL ctx / rows / row_off / bounds,
+ * a NULL slot with n_rows > 0, a NULL group with n_groups != 1, a table that is
+ * not one of the eight, zone >= Z, n_bounds outside 1 .. KACC_HIST_MAX_BOUNDS,
+ * n_groups outside 1 .. KACC_GROUP_MAX, n_groups * (n_bounds + 1) >
+ * KACC_HIST_MAX_BINS, keys not strictly ascending or a NaN bound, n_nodes > the
+ * context's nodes, all five outputs NULL.
+ *
+ * Asynchronous on `stream` (NULL = the context's): nothing is read back, there
+ * is no device-wide synchronize, and the scratch memory is stream-ordered.
+ * Every index is clamped: no input faults.                                    */
+#define KACC_HIST_MAX_BOUNDS 64u          /* largest n_bounds                          */
+#define KACC_HIST_MAX_BINS   (1u << 20)   /* largest n_groups * (n_bounds + 1)         */
+int kacc_group_hist(kacc_ctx *ctx, kacc_table t, uint32_t zone,
+                    const kacc_top_rows *rows,   /* the kind's rows of the last interval batch      */
+                    const uint32_t *group,       /* DEVICE [n_rows], or NULL: every row in group 0  */
+                    uint32_t n_groups,
+                    const uint64_t *bounds,      /* HOST [n_bounds]: value bits, ascending by key   */
+                    uint32_t n_bounds,
+                    const uint32_t *node_mask,   /* DEVICE [n_nodes], nonzero = listed; NULL = all  */
+                    uint64_t *out_bin,           /* DEVICE [n_groups * (n_bounds + 1)] or NULL      */
+                    uint64_t *out_cum,           /* DEVICE [n_groups * (n_bounds + 1)] or NULL      */
+                    uint64_t *out_sum,           /* DEVICE [n_groups] or NULL                       */
+                    uint64_t *out_nan,           /* DEVICE [n_groups] or NULL                       */
+                    uint64_t *out_unsummed,      /* DEVICE [n_groups] or NULL                       */
                     void *stream);
 
 /* Algorithmic HBM bytes of K consecutive intervals of these sizes: K times

@@ -57,6 +57,8 @@ KACC_TOP_MAX = 1024  # largest k of kacc_top_nodes / kacc_top_fleet
 KACC_GROUP_NONE = 0xFFFFFFFF  # kacc_group_sums: a row that belongs to no group
 KACC_GROUP_MAX = 65536  # largest n_groups
 KACC_GROUP_POWER_FRAC_BITS = 12  # out_power_fx: units of 2^-12 µW
+KACC_HIST_MAX_BOUNDS = 64  # kacc_group_hist: largest n_bounds
+KACC_HIST_MAX_BINS = 1 << 20  # largest n_groups * (n_bounds + 1)
 KACC_TRACKER_READ_CLEAR = 0x1  # kacc_tracker_read: clear the listed nodes' trackers behind the read
 
 # kacc_table enum, in header order: (name, numpy dtype)
@@ -112,6 +114,7 @@ EXPORTS = [
     "kacc_top_fleet",
     "kacc_select_above",
     "kacc_group_sums",
+    "kacc_group_hist",
     "kacc_zone_agg_create",
     "kacc_zone_agg_destroy",
     "kacc_zone_agg_read",
@@ -358,6 +361,8 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.kacc_select_above.argtypes = ([c_void_p, c_int, c_uint32, ctypes.c_uint64, POINTER(KaccTopRows), c_void_p,
                                        c_uint32] + [c_void_p] * 7)
     lib.kacc_group_sums.argtypes = ([c_void_p, c_int, POINTER(KaccTopRows), c_void_p, c_uint32] + [c_void_p] * 7)
+    lib.kacc_group_hist.argtypes = ([c_void_p, c_int, c_uint32, POINTER(KaccTopRows), c_void_p, c_uint32, c_void_p,
+                                     c_uint32] + [c_void_p] * 7)
     lib.kacc_last_error_copy.argtypes = [c_void_p, c_char_p, ctypes.c_size_t]
     lib.kacc_last_error_copy.restype = ctypes.c_size_t
     lib.kacc_create_multi.argtypes = [POINTER(c_int), c_int, POINTER(KaccConfig), POINTER(c_void_p),
@@ -767,6 +772,22 @@ class Accel:
                                              c_void_p(node_mask_ptr or None), c_void_p(out_count_ptr or None),
                                              c_void_p(out_energy_ptr or None), c_void_p(out_power_fx_ptr or None),
                                              c_void_p(out_power_ptr or None), c_void_p(out_dropped_ptr or None),
+                                             c_void_p(stream or None)))
+
+    def group_hist(self, table: str, zone: int, rows: KaccTopRows, group_ptr: int, n_groups: int, bounds,
+                   node_mask_ptr: int = 0, out_bin_ptr: int = 0, out_cum_ptr: int = 0, out_sum_ptr: int = 0,
+                   out_nan_ptr: int = 0, out_unsummed_ptr: int = 0, stream: int = 0) -> None:
+        """kacc_group_hist: the histogram of `table`'s values in `zone` over the running workloads of the
+        batch, per group id of each row (device u32 [n_rows]; 0 = every row in group 0, n_groups 1).
+        `bounds` is a sequence or array of u64 bit patterns (µJ, or the bits of the f64 µW), ascending
+        by key; bin and cum are u64 [n_groups * (len(bounds) + 1)], sum, nan and unsummed u64 [n_groups]
+        (device pointers, each optional)."""
+        b = np.ascontiguousarray(bounds, dtype=np.uint64)
+        self._check(self.lib.kacc_group_hist(self.ctx, TABLE_INDEX[table], zone, ctypes.byref(rows),
+                                             c_void_p(group_ptr or None), n_groups, c_void_p(b.ctypes.data), b.size,
+                                             c_void_p(node_mask_ptr or None), c_void_p(out_bin_ptr or None),
+                                             c_void_p(out_cum_ptr or None), c_void_p(out_sum_ptr or None),
+                                             c_void_p(out_nan_ptr or None), c_void_p(out_unsummed_ptr or None),
                                              c_void_p(stream or None)))
 
     def namespace_totals(self, n_ns: int, ns_pod_off_ptr: int, ns_pod_slot_ptr: int,

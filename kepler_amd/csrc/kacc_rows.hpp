@@ -1,5 +1,5 @@
-// The rows of an interval batch seen tile by tile (device helpers shared by kacc_select.hip and
-// kacc_group.hip; not part of the public ABI): the per-node flag word - is the node listed, and
+// The rows of an interval batch seen tile by tile (device helpers shared by kacc_select.hip,
+// kacc_group.hip and kacc_hist.hip; not part of the public ABI): the per-node flag word - is the node listed, and
 // which zones passed the guard of a derived power - and the search that finds a row's node in
 // row_off, so that workgroups tile the batch rows whatever the node sizes.
 #pragma once
