@@ -254,6 +254,12 @@ __device__ __forceinline__ double uniform_f64(double x) {
   return __longlong_as_double(static_cast<long long>(uniform_u64(static_cast<uint64_t>(__double_as_longlong(x)))));
 }
 __device__ __forceinline__ uint32_t uniform_u32(uint32_t x) { return __builtin_amdgcn_readfirstlane(x); }
+// a table pointer held in SGPRs, still known to be global memory (a pointer rebuilt from
+// an integer is generic: flat loads, which count on lgkmcnt too)
+template <typename T>
+__device__ __forceinline__ const T __attribute__((address_space(1))) *uniform_ptr(const T *p) {
+  return (const T __attribute__((address_space(1))) *)uniform_u64(reinterpret_cast<uint64_t>(p));
+}
 
 // Experiments (timing A/B only; results are identical): KACC_WT_PROC writes the
 // non-temporal row stores through the L2 (sc0 sc1 nt: no dirty line is left for
@@ -1125,9 +1131,14 @@ __device__ __forceinline__ void interval_node(const kacc_interval &b, const DevS
       a_w = b.pod_slot[q0 + j];
     }
   }
-  auto a_cap = [&]() -> uint64_t {
+  // the capacities as scalar values (capacities fit 31 bits, kacc_create): selected per lane
+  // from the kernel arguments they became a vector load, waited for with every load before it
+  const uint32_t cap_c = uniform_u32(static_cast<uint32_t>(st.ctr_slots));
+  const uint32_t cap_v = uniform_u32(static_cast<uint32_t>(st.vm_slots));
+  const uint32_t cap_q = uniform_u32(static_cast<uint32_t>(st.pod_slots));
+  auto a_cap = [&]() -> uint32_t {
     const uint32_t role = role_of();
-    return role == 1 ? st.ctr_slots : role == 2 ? st.vm_slots : role == 3 ? st.pod_slots : 0;
+    return role == 1 ? cap_c : role == 2 ? cap_v : role == 3 ? cap_q : 0u;
   };
   const uint32_t a_s = a_w & KACC_SLOT_MASK;
   auto a_ok_f = [&]() -> bool { return role_of() != 0 && a_s < a_cap(); };
@@ -1140,11 +1151,21 @@ __device__ __forceinline__ void interval_node(const kacc_interval &b, const DevS
   auto a_cpu_delta = [&]() {
     return role == 1 ? st.ctr_cpu_delta : role == 2 ? st.vm_cpu_delta : st.pod_cpu_delta;
   };
+  // Δ and the slot words go to LDS as they land (read after the first barrier):
+  // the Δ registers are free before the dependent loads below are issued
+#pragma unroll
+  for (int k = 0; k < kRowsPerThread; ++k) {
+    const uint32_t r = tid + k * kThreads;
+    if (r < rows) {
+      s_d[r] = d[k];
+      s_w[r] = w[k];
+    }
+  }
+  uint64_t prev[kRowsPerThread][Z];
   // second-level gathers (depend on the slot words).  A 64-row group with
   // consecutive slots is loaded 1 KiB-contiguous per wave instruction; a node
   // whose slots are not consecutive but span <= kRowsLds slots is swept in
   // slot order instead (see load_span_group).
-  uint64_t prev[kRowsPerThread][Z];
   uint32_t contig = 0;  // bit k: group k of this wave is transposed (wave-uniform)
   constexpr bool kSweepable =
       kTransposed<Z> && (V & (kVarNoTranspose | kVarNoSweep | kVarSkipProcs)) == 0;
@@ -1209,22 +1230,20 @@ __device__ __forceinline__ void interval_node(const kacc_interval &b, const DevS
   double a_total = 0.0;
   if (a_ok) {
     if constexpr (!kLateAgg<V>) load_row<Z>(a_energy(), agg_row(role, a_s), a_prev);
-    if (role != 2 && !(a_w & KACC_SLOT_NEW)) a_total = a_cpu_total()[a_s];
+    // the tables as scalar pointers: selected per lane from the kernel arguments they
+    // became a vector load of the pointer, waited for with every load before it (the
+    // rows' previous totals among them) before the running total's load could issue
+    if (role != 2 && !(a_w & KACC_SLOT_NEW)) {
+      const auto t_c = uniform_ptr(st.ctr_cpu_total), t_q = uniform_ptr(st.pod_cpu_total);
+      a_total = (role == 1 ? t_c : t_q)[a_s];
+    }
   } else {
 #pragma unroll
     for (int z = 0; z < Z; ++z) a_prev[z] = 0;
   }
   if (role != 0 && !a_ok) raise_err(st.err, kErrSlot);
 
-  // ---- B: stage Δ, ProcessTotalCPUTimeDelta (informer.go:330-333) ------------
-#pragma unroll
-  for (int k = 0; k < kRowsPerThread; ++k) {
-    const uint32_t r = tid + k * kThreads;
-    if (r < rows) {
-      s_d[r] = d[k];
-      s_w[r] = w[k];
-    }
-  }
+  // ---- B: Δ staged (above), ProcessTotalCPUTimeDelta (informer.go:330-333) ----
   __syncthreads();
   if constexpr (kStamp) {
     if (tid == 0) stamp[1] = __builtin_amdgcn_s_memrealtime();
