@@ -6,11 +6,13 @@
 // Every sum is an integer mod 2^64, so the order of the additions is free and the result is the
 // same bits for any tiling, any shard split and any number of GPUs.
 //
-//   node_prep   one thread per node: the listed flag and the guard bit of each zone, ONCE per
-//               node (kacc_rows.hpp; kacc_select.hip's)
+// The rows, their nodes' flag words, the tile prelude and the pass queue are the shared row
+// layer's (kacc_rows.hpp); this file adds the group bins on top.
+//
+//   node_prep   the shared layer's: one flag word per node
 //   bin         the groups' bins (count | dropped, Z energies, Z powers) fit in LDS: persistent
-//               workgroups, each walks every splits-th tile of kTile batch rows (the row's node
-//               by search in row_off), gathers every contributing row's record and adds it with
+//               workgroups, each walks every splits-th tile of kTile batch rows (located by the
+//               shared prelude), gathers every contributing row's record and adds it with
 //               64-bit LDS adds.  A group count small enough is replicated per lane subset, so
 //               the lanes of a wave do not queue on one bin
 //   rows, pass  more groups than LDS holds: `rows` classifies every row ONCE (one workgroup per
@@ -22,8 +24,8 @@
 //               accumulator with u64 atomics, consecutive lanes on consecutive words: one atomic
 //               per workgroup and bin word, never one per row
 //   finish      one thread per accumulator word: the outputs, and out_power from out_power_fx
-// Every index is clamped (rows to the batch, slots to slot 0, nodes by the search's range, group
-// ids by the pass's range), so no batch faults.
+// Every index is clamped (the shared layer's rules; group ids by the pass's range), so no batch
+// faults.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -42,37 +44,24 @@ constexpr uint32_t kTile = kThreads * kPer;       // rows per tile
 constexpr uint32_t kSmallWords = 4096;            // u64 of LDS bins: 32 KiB, three workgroups per CU
 constexpr uint32_t kBigWords = 9984;              // 78 KiB, two workgroups per CU: 1,109 groups at Z = 4
 constexpr uint32_t kPassWords = 9728;             // a pass's bins: 76 KiB, 1,080 groups at Z = 4
-constexpr uint32_t kQueue = 128;                  // a wave's queued rows in a pass (2 KiB per workgroup)
-constexpr uint32_t kPassPer = 16;                 // row words per lane and step of a pass
-constexpr uint32_t kPassTile = kThreads * kPassPer;
-constexpr uint32_t kCus = 256;                    // MI355X
-constexpr uint32_t kMaxCopies = 64;               // one copy of the bins per lane of a wave
+constexpr uint32_t kPassTile = kThreads * rows::kPassPer;  // the queues: 2 KiB per workgroup
 constexpr uint32_t kErrGroup = 1u << 13;          // a group id or a slot past its range, a row range
                                                   // outside the batch
-constexpr uint64_t kFxLimit = (1023ull + 50ull) << 52;  // the bits of 2^50: |p| at or past it is dropped
 // the row word of the `rows` pass: the group id, the node's guard bits above it
 constexpr uint32_t kWordGroup = 0xffffu, kWordGuardShift = 16;
 static_assert(KACC_GROUP_MAX <= kWordGroup + 1u && KACC_MAX_ZONES <= 8u, "a row word holds the id and the guard bits");
-using rows::kListed;
+using rows::derived_bits, rows::kCus, rows::kMaxCopies, rows::kQueue, rows::lds_add;
 using u64x2 = __attribute__((ext_vector_type(2))) unsigned long long;
 
 struct Args {
-  // the kind's records
-  const uint64_t *tab_e, *tab_p;  // the energy table; the stored power (pods) or NULL
-  uint32_t tab_stride;            // Z, or 2Z for the pod records
-  ProcDerive pd;                  // derived power
-  uint32_t Z, derived;
-  uint64_t cap;  // the kind's slot capacity
-  // the rows
-  uint32_t n_nodes, n_rows, tiles;
-  const uint32_t *row_off, *slot, *node_status, *node_mask, *group;
-  uint32_t n_groups;
+  rows::View v;
+  const uint32_t *group;
+  uint32_t n_groups, tiles;
   // the grid
   uint32_t splits;                // workgroups that share the tiles
   uint32_t copies, copy_stride;   // bin: 2^k copies of the bins, copy_stride u64 apart
   uint32_t bins, passes;          // pass: groups per pass; workgroup b takes pass b % passes, split b / passes
   // scratch
-  uint32_t *nflags;  // [n_nodes]
   uint64_t *acc;     // [n_groups] count | dropped << 32, [n_groups * Z] energy, [n_groups * Z] power_fx
   uint32_t *row_word, *row_node;  // [n_rows] (pass only)
   // the outputs
@@ -83,67 +72,19 @@ struct Args {
 };
 
 // fx(p) of the header for the f64 with these bits; a dropped value counts in `dropped`.
-__device__ __forceinline__ uint64_t power_fx(uint64_t bits, uint32_t &dropped) {
-  const bool keep = (bits & 0x7fffffffffffffffull) < kFxLimit;  // finite and |p| < 2^50
+__device__ __forceinline__ uint64_t fx_or_drop(uint64_t bits, uint32_t &dropped) {
+  bool keep;
+  const uint64_t fx = rows::power_fx(bits, keep);
   dropped += !keep;
-  const double p = __longlong_as_double(static_cast<long long>(keep ? bits : 0ull));
-  return static_cast<uint64_t>(static_cast<long long>(p * 4096.0));  // exact product, truncated toward zero
-}
-__device__ __forceinline__ uint64_t derived_bits(uint32_t f, uint32_t z, double ratio, double aP) {
-  return static_cast<uint64_t>(__double_as_longlong(((f >> z) & 1u) ? ratio * aP : 0.0));
-}
-__device__ __forceinline__ void lds_add(uint64_t *p, uint64_t v) {
-  atomicAdd(reinterpret_cast<unsigned long long *>(p), static_cast<unsigned long long>(v));
+  return fx;
 }
 
-__global__ __launch_bounds__(kThreads) void node_prep_kernel(const Args a) {
-  const uint32_t n = blockIdx.x * kThreads + threadIdx.x;
-  if (n >= a.n_nodes) return;
-  bool bad_range;
-  const uint32_t f = rows::node_flags(a.row_off, a.node_status, a.node_mask, a.pd, a.derived, a.Z, a.n_rows, n, bad_range);
-  if (bad_range) atomicOr(a.err, kErrGroup);  // left out
-  a.nflags[n] = f;
-}
-
-struct TileRows {  // a lane's kPer rows of a tile
-  bool in_batch[kPer], ok[kPer];  // ok: the row contributes
-  uint32_t r[kPer], sl[kPer], g[kPer], node[kPer], f[kPer];  // the slot is clamped to slot 0
-};
-// Classifies the tile's rows; true when a listed row of this lane has a slot or a group id out
-// of range.  No load sits behind a branch: a row past the batch is clamped to its last row.
-__device__ __forceinline__ bool classify_tile(const Args &a, uint32_t tile, uint32_t lane, uint32_t wave, TileRows &t) {
-  const rows::TileNodes tn = rows::tile_nodes(a.row_off, a.n_nodes, a.n_rows, tile, kTile, lane);
-  const uint64_t row0 = static_cast<uint64_t>(tile) * kTile + wave * (kPer * 64u) + lane;
-  const uint32_t last_row = a.n_rows - 1;
-  uint32_t w[kPer], hi[kPer];
+// The tile's rows, located and checked (the shared prelude): t.ok is "the row contributes".
+__device__ __forceinline__ void locate_tile(const Args &a, uint32_t tile, uint32_t lane, uint32_t wave,
+                                            rows::Located<kPer> &t) {
+  rows::locate<kPer>(a.v, a.group, tile, kTile, lane, wave, t);
 #pragma unroll
-  for (uint32_t u = 0; u < kPer; ++u) {
-    const uint64_t rr = row0 + u * 64u;
-    t.in_batch[u] = rr <= last_row;
-    t.r[u] = static_cast<uint32_t>(min(rr, static_cast<uint64_t>(last_row)));
-    w[u] = a.slot[t.r[u]];
-    t.g[u] = a.group[t.r[u]];
-    t.node[u] = tn.first;
-    hi[u] = tn.last;
-  }
-  for (uint32_t s = 0; s < tn.steps; ++s) {  // workgroup-uniform
-#pragma unroll
-    for (uint32_t u = 0; u < kPer; ++u) rows::node_step(a.row_off, t.r[u], t.node[u], hi[u]);
-  }
-  bool bad = false;
-#pragma unroll
-  for (uint32_t u = 0; u < kPer; ++u) {
-    const uint32_t n = t.node[u];
-    const uint32_t r0 = a.row_off[n], r1 = a.row_off[n + 1];
-    t.f[u] = a.nflags[n];
-    const bool listed = t.in_batch[u] && r0 <= t.r[u] && t.r[u] < r1 && (t.f[u] & kListed);
-    const uint32_t s = w[u] & KACC_SLOT_MASK;
-    const bool in = s < a.cap, gin = t.g[u] < a.n_groups;
-    bad = bad || (listed && (!in || (!gin && t.g[u] != KACC_GROUP_NONE)));  // left out
-    t.ok[u] = listed && in && gin;
-    t.sl[u] = in ? s : 0u;
-  }
-  return bad;
+  for (uint32_t u = 0; u < kPer; ++u) rows::check_row(a.v, a.n_groups, t, u);
 }
 
 // Adds one row's record (slot sl below the capacity, its node, the node's guard bits f) into bin
@@ -151,11 +92,11 @@ __device__ __forceinline__ bool classify_tile(const Args &a, uint32_t tile, uint
 template <uint32_t kZ>
 __device__ __forceinline__ void add_one(const Args &a, uint32_t sl, uint32_t node, uint32_t f, uint32_t bin,
                                         uint64_t *b_cd, uint64_t *b_e, uint64_t *b_p) {
-  const uint32_t Z = kZ ? kZ : a.Z;
-  const uint64_t *se = a.tab_e + static_cast<uint64_t>(sl) * a.tab_stride;
-  const uint64_t *sp = a.derived ? reinterpret_cast<const uint64_t *>(a.pd.active_power) + static_cast<uint64_t>(node) * Z
-                                 : a.tab_p + static_cast<uint64_t>(sl) * a.tab_stride;
-  const double ratio = a.derived ? a.pd.ratio[sl] : 0.0;
+  const uint32_t Z = kZ ? kZ : a.v.Z;
+  const uint64_t *se = a.v.tab_e + static_cast<uint64_t>(sl) * a.v.tab_stride;
+  const uint64_t *sp = a.v.derived ? reinterpret_cast<const uint64_t *>(a.v.pd.active_power) + static_cast<uint64_t>(node) * Z
+                                 : a.v.tab_p + static_cast<uint64_t>(sl) * a.v.tab_stride;
+  const double ratio = a.v.derived ? a.v.pd.ratio[sl] : 0.0;
   uint32_t dropped = 0;
   if constexpr (kZ == 4) {
     const u64x2 e0 = reinterpret_cast<const u64x2 *>(se)[0], e1 = reinterpret_cast<const u64x2 *>(se)[1];
@@ -164,16 +105,16 @@ __device__ __forceinline__ void add_one(const Args &a, uint32_t sl, uint32_t nod
 #pragma unroll
     for (uint32_t z = 0; z < 4; ++z) {
       const uint64_t bits =
-          a.derived ? derived_bits(f, z, ratio, __longlong_as_double(static_cast<long long>(pw[z]))) : pw[z];
+          a.v.derived ? derived_bits(f, z, ratio, __longlong_as_double(static_cast<long long>(pw[z]))) : pw[z];
       lds_add(&b_e[bin * 4u + z], ew[z]);
-      lds_add(&b_p[bin * 4u + z], power_fx(bits, dropped));
+      lds_add(&b_p[bin * 4u + z], fx_or_drop(bits, dropped));
     }
   } else {
     for (uint32_t z = 0; z < Z; ++z) {
       const uint64_t pw = sp[z];
-      const uint64_t bits = a.derived ? derived_bits(f, z, ratio, __longlong_as_double(static_cast<long long>(pw))) : pw;
+      const uint64_t bits = a.v.derived ? derived_bits(f, z, ratio, __longlong_as_double(static_cast<long long>(pw))) : pw;
       lds_add(&b_e[bin * Z + z], se[z]);
-      lds_add(&b_p[bin * Z + z], power_fx(bits, dropped));
+      lds_add(&b_p[bin * Z + z], fx_or_drop(bits, dropped));
     }
   }
   lds_add(&b_cd[bin], 1ull | static_cast<uint64_t>(dropped) << 32);
@@ -197,16 +138,16 @@ __device__ __forceinline__ void add_rows(const Args &a, const bool (&mine)[kPer]
         const uint32_t u = c + j;
         e[j][0] = e[j][1] = p[j][0] = p[j][1] = u64x2{0ull, 0ull};
         ratio[j] = 0.0;
-        if (a.cap != 0) {  // uniform
-          const u64x2 *se = reinterpret_cast<const u64x2 *>(a.tab_e + static_cast<uint64_t>(sl[u]) * a.tab_stride);
+        if (a.v.cap != 0) {  // uniform
+          const u64x2 *se = reinterpret_cast<const u64x2 *>(a.v.tab_e + static_cast<uint64_t>(sl[u]) * a.v.tab_stride);
           e[j][0] = se[0];
           e[j][1] = se[1];
           const u64x2 *sp;
-          if (a.derived) {  // uniform
-            ratio[j] = a.pd.ratio[sl[u]];
-            sp = reinterpret_cast<const u64x2 *>(a.pd.active_power + static_cast<uint64_t>(node[u]) * 4u);
+          if (a.v.derived) {  // uniform
+            ratio[j] = a.v.pd.ratio[sl[u]];
+            sp = reinterpret_cast<const u64x2 *>(a.v.pd.active_power + static_cast<uint64_t>(node[u]) * 4u);
           } else {
-            sp = reinterpret_cast<const u64x2 *>(a.tab_p + static_cast<uint64_t>(sl[u]) * a.tab_stride);
+            sp = reinterpret_cast<const u64x2 *>(a.v.tab_p + static_cast<uint64_t>(sl[u]) * a.v.tab_stride);
           }
           p[j][0] = sp[0];
           p[j][1] = sp[1];
@@ -222,9 +163,9 @@ __device__ __forceinline__ void add_rows(const Args &a, const bool (&mine)[kPer]
 #pragma unroll
         for (uint32_t z = 0; z < 4; ++z) {
           const uint64_t bits =
-              a.derived ? derived_bits(f[u], z, ratio[j], __longlong_as_double(static_cast<long long>(pw[z]))) : pw[z];
+              a.v.derived ? derived_bits(f[u], z, ratio[j], __longlong_as_double(static_cast<long long>(pw[z]))) : pw[z];
           lds_add(&b_e[bin[u] * 4u + z], ew[z]);
-          lds_add(&b_p[bin[u] * 4u + z], power_fx(bits, dropped));
+          lds_add(&b_p[bin[u] * 4u + z], fx_or_drop(bits, dropped));
         }
         lds_add(&b_cd[bin[u]], 1ull | static_cast<uint64_t>(dropped) << 32);
       }
@@ -240,7 +181,7 @@ __device__ __forceinline__ void add_rows(const Args &a, const bool (&mine)[kPer]
 // the accumulator's planes, consecutive lanes on consecutive words.
 __device__ __forceinline__ void flush_bins(const Args &a, const uint64_t *s_bin, uint32_t copies, uint32_t g0,
                                            uint32_t nloc, uint32_t tid) {
-  const uint32_t Z = a.Z, n_e = nloc * Z;
+  const uint32_t Z = a.v.Z, n_e = nloc * Z;
   for (uint32_t i = tid; i < nloc + 2u * n_e; i += kThreads) {
     uint64_t v = 0;
     for (uint32_t c = 0; c < copies; ++c) v += s_bin[c * a.copy_stride + i];
@@ -261,15 +202,16 @@ template <uint32_t kZ, uint32_t kLds>
 __global__ __launch_bounds__(kThreads, kLds == kSmallWords ? 3 : 2) void bin_kernel(const Args a) {
   __shared__ uint64_t s_bin[kLds];
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  const uint32_t Z = kZ ? kZ : a.Z, G = a.n_groups;
+  const uint32_t Z = kZ ? kZ : a.v.Z, G = a.n_groups;
   for (uint32_t i = tid; i < a.copies * a.copy_stride; i += kThreads) s_bin[i] = 0;  // <= kLds (host)
   __syncthreads();
   uint64_t *const b_cd = s_bin + (lane & (a.copies - 1u)) * a.copy_stride;
   uint64_t *const b_e = b_cd + G, *const b_p = b_e + G * Z;
   bool bad = false;
   for (uint32_t tile = blockIdx.x; tile < a.tiles; tile += a.splits) {  // workgroup-uniform
-    TileRows t;
-    bad = classify_tile(a, tile, lane, wave, t) || bad;
+    rows::Located<kPer> t;
+    locate_tile(a, tile, lane, wave, t);
+    bad = t.bad || bad;
     add_rows<kZ>(a, t.ok, t.sl, t.node, t.f, t.g, b_cd, b_e, b_p);
   }
   if (bad) atomicOr(a.err, kErrGroup);
@@ -281,20 +223,15 @@ __global__ __launch_bounds__(kThreads, kLds == kSmallWords ? 3 : 2) void bin_ker
 // row that does not contribute) and the node of every row of the batch.
 __global__ __launch_bounds__(kThreads) void rows_kernel(const Args a) {
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  TileRows t;
-  if (classify_tile(a, blockIdx.x, lane, wave, t)) atomicOr(a.err, kErrGroup);
+  rows::Located<kPer> t;
+  locate_tile(a, blockIdx.x, lane, wave, t);
+  if (t.bad) atomicOr(a.err, kErrGroup);
 #pragma unroll
   for (uint32_t u = 0; u < kPer; ++u) {
     if (!t.in_batch[u]) continue;
     a.row_word[t.r[u]] = t.ok[u] ? t.g[u] | (t.f[u] & ((1u << KACC_MAX_ZONES) - 1u)) << kWordGuardShift : KACC_GROUP_NONE;
     a.row_node[t.r[u]] = t.node[u];
   }
-}
-
-__device__ __forceinline__ void wave_lds_fence() {  // a wave's LDS writes before its reads (kacc_select.hip's)
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // A pass's range of groups in LDS; the rows by their row words.  About one row word in `passes`
@@ -305,7 +242,7 @@ __global__ __launch_bounds__(kThreads, 2) void pass_kernel(const Args a) {
   __shared__ uint64_t s_bin[kPassWords];
   __shared__ uint32_t s_q[kThreads / 64][kQueue];
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  const uint32_t Z = kZ ? kZ : a.Z;
+  const uint32_t Z = kZ ? kZ : a.v.Z;
   const uint32_t pass = blockIdx.x % a.passes, split = blockIdx.x / a.passes;
   const uint32_t g0 = pass * a.bins;  // < n_groups
   const uint32_t nloc = min(a.bins, a.n_groups - g0);
@@ -313,8 +250,7 @@ __global__ __launch_bounds__(kThreads, 2) void pass_kernel(const Args a) {
   __syncthreads();
   uint64_t *const b_cd = s_bin, *const b_e = b_cd + nloc, *const b_p = b_e + nloc * Z;
   uint32_t *const q = s_q[wave];
-  const uint32_t last_row = a.n_rows - 1;
-  const uint32_t pass_tiles = static_cast<uint32_t>((static_cast<uint64_t>(a.n_rows) + kPassTile - 1) / kPassTile);
+  const uint32_t last_row = a.v.n_rows - 1;
 
   // the queued rows q[0 .. n) of this wave, n <= 64, one per lane
   auto drain = [&](uint32_t n) {
@@ -322,40 +258,15 @@ __global__ __launch_bounds__(kThreads, 2) void pass_kernel(const Args a) {
     const uint32_t r = min(q[lane], last_row);
     const uint32_t word = a.row_word[r];
     const uint32_t bin = min((word & kWordGroup) - g0, nloc - 1u);  // the pass's: checked when it was queued
-    const uint32_t s = a.slot[r] & KACC_SLOT_MASK;
-    const uint32_t sl = s < a.cap ? s : 0u;  // below the capacity when the row word was written
-    const uint32_t node = min(a.row_node[r], a.n_nodes - 1u);
+    const uint32_t s = a.v.slot[r] & KACC_SLOT_MASK;
+    const uint32_t sl = s < a.v.cap ? s : 0u;  // below the capacity when the row word was written
+    const uint32_t node = min(a.row_node[r], a.v.n_nodes - 1u);
     add_one<kZ>(a, sl, node, word >> kWordGuardShift, bin, b_cd, b_e, b_p);
   };
 
-  uint32_t qn = 0;  // wave-uniform: the queued rows, < 64 between steps
-  for (uint32_t tile = split; tile < pass_tiles; tile += a.splits) {  // workgroup-uniform
-    const uint64_t row0 = static_cast<uint64_t>(tile) * kPassTile + wave * (kPassPer * 64u) + lane;
-    uint32_t word[kPassPer];
-#pragma unroll
-    for (uint32_t u = 0; u < kPassPer; ++u)  // a row past the batch is clamped to its last row
-      word[u] = a.row_word[static_cast<uint32_t>(min(row0 + u * 64u, static_cast<uint64_t>(last_row)))];
-#pragma unroll
-    for (uint32_t u = 0; u < kPassPer; ++u) {
-      const uint64_t rr = row0 + u * 64u;
-      const bool mine = rr <= last_row && word[u] != KACC_GROUP_NONE && (word[u] & kWordGroup) - g0 < nloc;
-      const uint64_t m = __ballot(mine);
-      if (m == 0) continue;  // wave-uniform
-      if (mine) q[qn + static_cast<uint32_t>(__popcll(m & ((1ull << lane) - 1ull)))] = static_cast<uint32_t>(rr);
-      qn += static_cast<uint32_t>(__popcll(m));  // <= 127 < kQueue
-      if (qn >= 64u) {
-        wave_lds_fence();
-        drain(64u);
-        const uint32_t rest = qn - 64u;  // < 64
-        const uint32_t moved = q[64u + min(lane, 63u)];
-        wave_lds_fence();
-        if (lane < rest) q[lane] = moved;
-        qn = rest;
-      }
-    }
-  }
-  wave_lds_fence();
-  drain(qn);
+  rows::pass_queue<kThreads>(
+      a.row_word, a.v.n_rows, split, a.splits, lane, wave, q,
+      [&](uint32_t word) { return word != KACC_GROUP_NONE && (word & kWordGroup) - g0 < nloc; }, drain);
   __syncthreads();
   flush_bins(a, s_bin, 1u, g0, nloc, tid);
 }
@@ -364,7 +275,7 @@ __global__ __launch_bounds__(kThreads, 2) void pass_kernel(const Args a) {
 // correctly rounded to f64, times 2^-12 (exact).
 __global__ __launch_bounds__(kThreads) void finish_kernel(const Args a) {
   const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kThreads + threadIdx.x;
-  const uint64_t G = a.n_groups, GZ = G * a.Z;
+  const uint64_t G = a.n_groups, GZ = G * a.v.Z;
   if (i < G) {
     const uint64_t cd = a.acc[i];
     if (a.out_count) a.out_count[i] = static_cast<uint32_t>(cd);
@@ -389,45 +300,22 @@ int kacc_group_sums(kacc_ctx *ctx, kacc_kind kind, const kacc_top_rows *rows, co
   using namespace kacc::grp;
   const char *fn = "kacc_group_sums";
   if (!ctx) return KACC_EINVAL;
-  if (kind != KACC_KIND_PROC && kind != KACC_KIND_CTR && kind != KACC_KIND_VM && kind != KACC_KIND_POD)
-    return kacc_fail(ctx, KACC_EINVAL, "%s: unknown kind %d", fn, (int)kind);
+  Args a{};
+  int rc = kacc::rows::resolve_kind(ctx, fn, kind);
+  if (rc != KACC_OK) return rc;
   if (!rows) return kacc_fail(ctx, KACC_EINVAL, "%s: NULL argument", fn);
   if (n_groups < 1 || n_groups > KACC_GROUP_MAX)
     return kacc_fail(ctx, KACC_EINVAL, "%s: n_groups %u outside 1 .. %u", fn, n_groups, KACC_GROUP_MAX);
-  if (rows->n_nodes > ctx->cfg.nodes)
-    return kacc_fail(ctx, KACC_EINVAL, "%s: n_nodes %u > the context's %llu nodes", fn, rows->n_nodes,
-                     (unsigned long long)ctx->cfg.nodes);
-  if (!rows->row_off || (rows->n_rows && (!rows->slot || !group)))
-    return kacc_fail(ctx, KACC_EINVAL, "%s: NULL row array", fn);
+  if ((rc = kacc::rows::resolve(ctx, fn, kind, rows, node_mask, &a.v)) != KACC_OK) return rc;
+  if (rows->n_rows && !group) return kacc_fail(ctx, KACC_EINVAL, "%s: NULL row array", fn);
   if (!out_count && !out_energy && !out_power_fx && !out_power && !out_dropped)
     return kacc_fail(ctx, KACC_EINVAL, "%s: no output array", fn);
   KACC_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
   kacc::TimingScope timing(ctx);
 
-  Args a{};
-  const uint32_t Z = ctx->cfg.zones, W = 1u + 2u * Z;
-  const bool pod = kind == KACC_KIND_POD;
-  const int te = pod ? KACC_T_POD_ENERGY : kind == KACC_KIND_PROC ? KACC_T_PROC_ENERGY
-                 : kind == KACC_KIND_CTR ? KACC_T_CTR_ENERGY : KACC_T_VM_ENERGY;
-  a.cap = kind == KACC_KIND_PROC ? ctx->cfg.proc_slots
-          : kind == KACC_KIND_CTR ? ctx->cfg.ctr_slots
-          : kind == KACC_KIND_VM ? ctx->cfg.vm_slots
-                                 : ctx->cfg.pod_slots;
-  a.pd = kacc_derive(ctx, pod ? KACC_KIND_PROC : kind);
-  a.derived = !pod;
-  a.tab_stride = pod ? 2 * Z : Z;
-  a.tab_e = static_cast<const uint64_t *>(ctx->tables[te]);
-  a.tab_p = pod ? static_cast<const uint64_t *>(ctx->tables[KACC_T_POD_POWER]) : nullptr;  // Z words into the record
-  a.Z = Z;
-  a.n_nodes = rows->n_nodes;
-  a.n_rows = rows->n_rows;
-  // without a node no row is listed
-  a.tiles = a.n_nodes ? static_cast<uint32_t>((static_cast<uint64_t>(a.n_rows) + kTile - 1) / kTile) : 0u;
-  a.row_off = rows->row_off;
-  a.slot = rows->slot;
-  a.node_status = rows->node_status;
-  a.node_mask = node_mask;
+  const uint32_t Z = a.v.Z, W = 1u + 2u * Z;
+  a.tiles = a.v.n_nodes ? kacc::rows::tiles_of(a.v.n_rows, kTile) : 0u;  // without a node no row is listed
   a.group = group;
   a.n_groups = n_groups;
   a.out_count = out_count;
@@ -455,26 +343,27 @@ int kacc_group_sums(kacc_ctx *ctx, kacc_kind kind, const kacc_top_rows *rows, co
     a.copy_stride = 0;
   }
   const uint32_t wgs = kCus * (lds == kSmallWords ? 3u : 2u);
-  const uint32_t pass_tiles = static_cast<uint32_t>((static_cast<uint64_t>(a.n_rows) + kPassTile - 1) / kPassTile);
+  const uint32_t pass_tiles = kacc::rows::tiles_of(a.v.n_rows, kPassTile);
   a.splits = std::max(1u, a.passes > 1 ? std::min(pass_tiles, wgs / a.passes) : std::min(a.tiles, wgs));
 
   // temporaries, stream ordered: the accumulator, the node flags and, for passes, the row words
   // and nodes
   const uint64_t acc_words = static_cast<uint64_t>(n_groups) * W;
-  const uint64_t row_words = a.passes > 1 && a.tiles ? a.n_rows : 0;
+  const uint64_t row_words = a.passes > 1 && a.tiles ? a.v.n_rows : 0;
   uint64_t *tmp = nullptr;
-  KACC_HIP(ctx, hipMallocAsync(reinterpret_cast<void **>(&tmp), 8 * acc_words + 4ull * a.n_nodes + 8 * row_words, st));
+  KACC_HIP(ctx, hipMallocAsync(reinterpret_cast<void **>(&tmp), 8 * acc_words + 4ull * a.v.n_nodes + 8 * row_words, st));
   a.acc = tmp;
-  a.nflags = reinterpret_cast<uint32_t *>(tmp + acc_words);
-  a.row_word = a.nflags + a.n_nodes;
+  a.v.nflags = reinterpret_cast<uint32_t *>(tmp + acc_words);
+  a.row_word = a.v.nflags + a.v.n_nodes;
   a.row_node = a.row_word + row_words;
-  int rc = KACC_OK;
   if (hipMemsetAsync(a.acc, 0, 8 * acc_words, st) != hipSuccess) rc = kacc_fail(ctx, KACC_EHIP, "%s: memset", fn);
 
   if (rc == KACC_OK) {
     (void)hipGetLastError();  // clear a stale error of an earlier call
     const dim3 block(kThreads);
-    if (a.n_nodes) KACC_LAUNCH(node_prep_kernel, dim3((a.n_nodes + kThreads - 1) / kThreads), block, 0, st, a);
+    if (a.v.n_nodes)
+      KACC_LAUNCH(kacc::rows::node_prep_kernel<kThreads>, dim3((a.v.n_nodes + kThreads - 1) / kThreads), block, 0, st, a.v,
+                  a.err, kErrGroup, static_cast<uint64_t *>(nullptr));
     if (a.tiles) {
       const bool z4 = Z == 4;
       if (a.passes > 1) {

@@ -11,10 +11,12 @@
 // A group's counters are C = n_bounds + 3 u32 words - the n_bounds + 1 bins, `nan`, `unsummed` -
 // plus one u64 sum word.
 //
-//   node_prep   one thread per node: the listed flag and the guard bit of each zone, ONCE per
-//               node (kacc_rows.hpp; kacc_select.hip's)
+// The rows, their values, their nodes' flag words, the tile prelude and the pass queue are the
+// shared row layer's (kacc_rows.hpp); this file adds the bounds and the counters on top.
+//
+//   node_prep   the shared layer's: one flag word per node
 //   bin         the groups' counters and sums fit in LDS: persistent workgroups, each walks every
-//               splits-th tile of kTile batch rows (the row's node by search in row_off), loads
+//               splits-th tile of kTile batch rows (located by the shared prelude), loads
 //               every row's value, counts the bounds below it (a compare-and-add loop over the
 //               bounds' keys, which are kernel arguments: uniform registers) and adds 1 to the
 //               bin with one 32-bit LDS add, and the row's sum word with one 64-bit LDS add
@@ -32,8 +34,8 @@
 //               u64 accumulator with atomics, consecutive lanes on consecutive words: one atomic
 //               per workgroup and word, never one per row
 //   finish      one thread per bin: the outputs, out_cum as the prefix over the group's bins
-// Every index is clamped (rows to the batch, slots to slot 0, nodes by the search's range, group
-// ids and counter indices by the pass's range), so no batch faults.
+// Every index is clamped (the shared layer's rules; group ids and counter indices by the
+// pass's range), so no batch faults.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -54,44 +56,33 @@ constexpr uint32_t kTile = kThreads * kPer;       // rows per tile (kBigThreads 
 constexpr uint32_t kSmallWords = 8192;            // 32 KiB, three workgroups per CU: replicated counters
 constexpr uint32_t kBigWords = 20096;             // 78.5 KiB: 1,004 groups at 15 bounds
 constexpr uint32_t kPassWords = 19200;            // a pass's counters: 75 KiB, 960 groups at 15 bounds
-constexpr uint32_t kQueue = 128;                  // a wave's queued rows in a pass (4 KiB per workgroup)
-constexpr uint32_t kPassPer = 16;                 // row words per lane and step of a pass
-constexpr uint32_t kPassTile = kThreads * kPassPer;
-constexpr uint32_t kCus = 256;                    // MI355X
-constexpr uint32_t kMaxCopies = 64;               // one copy of the counters per lane of a wave
+constexpr uint32_t kPassTile = kThreads * rows::kPassPer;  // the queues: 4 KiB per workgroup
 constexpr uint32_t kErrHist = 1u << 14;           // a group id or a slot past its range, a row range
                                                   // outside the batch
-constexpr uint64_t kFxLimit = (1023ull + 50ull) << 52;  // the bits of 2^50: |p| at or past it adds no sum
 // the row word of the `rows` pass: the group id, the counter index within the group above it
 // (a bin, or n_bounds + 1 = `nan`), then the two flags
 constexpr uint32_t kWordGroup = 0xffffu, kWordIdxShift = 16, kWordIdx = 0x7fu;
 constexpr uint32_t kWordUnsummed = 1u << 23, kWordSum = 1u << 24, kWordNone = 0xffffffffu;
 static_assert(KACC_GROUP_MAX <= kWordGroup + 1u && KACC_HIST_MAX_BOUNDS + 2u <= kWordIdx,
               "a row word holds the group id and the counter index");
-using rows::kListed;
-
-enum Src { kEnergy = 0, kStored = 1, kDerived = 2 };  // the table of the values
+using rows::kCus, rows::kMaxCopies, rows::kQueue, rows::lds_add;
+using rows::kDerived, rows::kEnergy, rows::kStored;  // the table of the values
 
 struct Args {
+  rows::View v;
   // the values' table
-  const uint64_t *words;  // energy / stored power words of `zone`: words[slot * stride]
-  uint32_t stride;        // Z, or 2Z for the pod records
-  ProcDerive pd;          // derived power
-  uint32_t zone, Z, derived;
-  uint64_t cap;  // the kind's slot capacity
+  const uint64_t *words;  // energy / stored power words of `zone`: words[slot * v.tab_stride]
+  uint32_t zone;
   // the bounds
   uint32_t n_bounds;
   uint64_t key[KACC_HIST_MAX_BOUNDS];  // strictly ascending
-  // the rows
-  uint32_t n_nodes, n_rows, tiles;
-  const uint32_t *row_off, *slot, *node_status, *node_mask, *group;  // group NULL: every row in group 0
-  uint32_t n_groups;
+  const uint32_t *group;  // NULL: every row in group 0
+  uint32_t n_groups, tiles;
   // the grid
   uint32_t splits;                        // workgroups that share the tiles
   uint32_t copies, cnt_stride, sum_stride;  // bin: 2^k copies; a copy's counters (u32) and sums (u64) apart
   uint32_t bins, passes;                  // pass: groups per pass; workgroup b takes pass b % passes, split b / passes
   // scratch
-  uint32_t *nflags;   // [n_nodes]
   uint64_t *acc;      // [n_groups * C] the counters, [n_groups] the sums
   uint32_t *row_word; // [n_rows] (pass only)
   uint64_t *row_fx;   // [n_rows] (pass only)
@@ -100,86 +91,29 @@ struct Args {
   uint32_t *err;
 };
 
-// The order rule's key of a power (header; kacc_top.hip's): NaN lowest, the zeros equal, else
-// the IEEE order.
-__host__ __device__ __forceinline__ uint64_t power_key(uint64_t b) {
-  const uint32_t hi = static_cast<uint32_t>(b >> 32), lo = static_cast<uint32_t>(b);
-  const uint32_t mag = hi & 0x7fffffffu;
-  if (mag > 0x7ff00000u || (mag == 0x7ff00000u && lo != 0)) return 0;  // NaN
-  if ((mag | lo) == 0) return 0x8000000000000000ull;                   // ±0
-  return (hi >> 31) ? ~b : (b | 0x8000000000000000ull);
-}
-// fx(p) of the header (kacc_group.hip's) for the f64 with these bits; keep: it adds to the sum.
-__device__ __forceinline__ uint64_t power_fx(uint64_t bits, bool &keep) {
-  keep = (bits & 0x7fffffffffffffffull) < kFxLimit;  // finite and |p| < 2^50
-  const double p = __longlong_as_double(static_cast<long long>(keep ? bits : 0ull));
-  return static_cast<uint64_t>(static_cast<long long>(p * 4096.0));  // exact product, truncated toward zero
-}
-__device__ __forceinline__ void lds_add(uint64_t *p, uint64_t v) {
-  atomicAdd(reinterpret_cast<unsigned long long *>(p), static_cast<unsigned long long>(v));
-}
-
-__global__ __launch_bounds__(kThreads) void node_prep_kernel(const Args a) {
-  const uint32_t n = blockIdx.x * kThreads + threadIdx.x;
-  if (n >= a.n_nodes) return;
-  bool bad_range;
-  const uint32_t f = rows::node_flags(a.row_off, a.node_status, a.node_mask, a.pd, a.derived, a.Z, a.n_rows, n, bad_range);
-  if (bad_range) atomicOr(a.err, kErrHist);  // left out
-  a.nflags[n] = f;
-}
-
 struct TileRows {  // a lane's kPer rows of a tile
   bool in_batch[kPer], ok[kPer], uns[kPer];  // ok: the row contributes; uns: binned, but no sum word
   uint32_t r[kPer], g[kPer], idx[kPer];      // idx: the counter within the group (a bin, or `nan`)
   uint64_t fx[kPer];                         // the sum word
 };
-// Classifies the tile's rows and evaluates them; true when a listed row of this lane has a slot
-// or a group id out of range.  No load sits behind a data-dependent branch: a row past the
-// batch is clamped to its last row, a bad slot to slot 0.
+// Locates the tile's rows (the shared prelude) and evaluates them; true when a listed row of
+// this lane has a slot or a group id out of range.
 template <int kSrc, uint32_t kT>  // kT: the workgroup's threads, a tile is kT * kPer rows
 __device__ __forceinline__ bool classify_tile(const Args &a, uint32_t tile, uint32_t lane, uint32_t wave, TileRows &t) {
-  const rows::TileNodes tn = rows::tile_nodes(a.row_off, a.n_nodes, a.n_rows, tile, kT * kPer, lane);
-  const uint64_t row0 = static_cast<uint64_t>(tile) * (kT * kPer) + wave * (kPer * 64u) + lane;
-  const uint32_t last_row = a.n_rows - 1;
-  uint32_t w[kPer], node[kPer], hi[kPer];
-#pragma unroll
-  for (uint32_t u = 0; u < kPer; ++u) {
-    const uint64_t rr = row0 + u * 64u;
-    t.in_batch[u] = rr <= last_row;
-    t.r[u] = static_cast<uint32_t>(min(rr, static_cast<uint64_t>(last_row)));
-    w[u] = a.slot[t.r[u]];
-    t.g[u] = a.group ? a.group[t.r[u]] : 0u;  // uniform
-    node[u] = tn.first;
-    hi[u] = tn.last;
-  }
-  for (uint32_t s = 0; s < tn.steps; ++s) {  // workgroup-uniform
-#pragma unroll
-    for (uint32_t u = 0; u < kPer; ++u) rows::node_step(a.row_off, t.r[u], node[u], hi[u]);
-  }
-  bool bad = false;
+  rows::Located<kPer> l;
+  rows::locate<kPer>(a.v, a.group, tile, kT * kPer, lane, wave, l);
   uint64_t v[kPer], key[kPer];
 #pragma unroll
   for (uint32_t u = 0; u < kPer; ++u) {
-    const uint32_t n = node[u];
-    const uint32_t r0 = a.row_off[n], r1 = a.row_off[n + 1];
-    const uint32_t f = a.nflags[n];
-    const bool listed = t.in_batch[u] && r0 <= t.r[u] && t.r[u] < r1 && (f & kListed);
-    const uint32_t s = w[u] & KACC_SLOT_MASK;
-    const bool in = s < a.cap, gin = t.g[u] < a.n_groups;
-    bad = bad || (listed && (!in || (!gin && t.g[u] != KACC_GROUP_NONE)));  // left out
-    t.ok[u] = listed && in && gin;
-    const uint64_t sl = in ? s : 0u;
+    rows::check_row(a.v, a.n_groups, l, u);
+    t.in_batch[u] = l.in_batch[u];
+    t.ok[u] = l.ok[u];
+    t.r[u] = l.r[u];
+    t.g[u] = l.g[u];
     v[u] = 0;
-    if (a.cap != 0) {  // uniform
-      if constexpr (kSrc == kDerived) {
-        const double ratio = a.pd.ratio[sl];
-        const double aP = a.pd.active_power[static_cast<uint64_t>(n) * a.Z + a.zone];
-        v[u] = static_cast<uint64_t>(__double_as_longlong(((f >> a.zone) & 1u) ? ratio * aP : 0.0));
-      } else {
-        v[u] = a.words[sl * a.stride];
-      }
-    }
-    key[u] = kSrc == kEnergy ? v[u] : power_key(v[u]);
+    if (a.v.cap != 0)  // uniform
+      v[u] = rows::value_bits<kSrc>(a.words, a.v.tab_stride, a.v.pd, a.v.Z, a.zone, l.sl[u], l.node[u], l.f[u]);
+    key[u] = kSrc == kEnergy ? v[u] : rows::power_key(v[u]);
     t.idx[u] = 0;
   }
   for (uint32_t i = 0; i < a.n_bounds; ++i) {  // uniform: the bound's key is a scalar
@@ -194,13 +128,13 @@ __device__ __forceinline__ bool classify_tile(const Args &a, uint32_t tile, uint
       t.uns[u] = false;
     } else {
       bool keep;
-      t.fx[u] = power_fx(v[u], keep);
+      t.fx[u] = rows::power_fx(v[u], keep);
       const bool nan = key[u] == 0;  // only a NaN has key 0
       t.idx[u] = nan ? a.n_bounds + 1u : t.idx[u];
       t.uns[u] = !keep && !nan;
     }
   }
-  return bad;
+  return l.bad;
 }
 
 // The flush: the workgroup's counters and sums of groups [g0, g0 + nloc) (the copies summed)
@@ -275,12 +209,6 @@ __global__ __launch_bounds__(kThreads) void rows_kernel(const Args a) {
   }
 }
 
-__device__ __forceinline__ void wave_lds_fence() {  // a wave's LDS writes before its reads (kacc_select.hip's)
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // A pass's range of groups in LDS; the rows by their row words.  About one row word in `passes`
 // is the pass's, so a wave first queues its rows (ballot and popcount, in LDS) and adds 64
 // queued rows at a time, one per lane: the sum words' loads of 64 rows are in flight together.
@@ -298,8 +226,7 @@ __global__ __launch_bounds__(kThreads, 4) void pass_kernel(const Args a) {
   uint64_t *const b_sum = s_mem;
   uint32_t *const b_cnt = s32 + 2u * nloc;
   uint32_t *const q = s_q[wave];
-  const uint32_t last_row = a.n_rows - 1;
-  const uint32_t pass_tiles = static_cast<uint32_t>((static_cast<uint64_t>(a.n_rows) + kPassTile - 1) / kPassTile);
+  const uint32_t last_row = a.v.n_rows - 1;
 
   // the queued rows q[0 .. n) of this wave, n <= 64, one per lane
   auto drain = [&](uint32_t n) {
@@ -314,34 +241,9 @@ __global__ __launch_bounds__(kThreads, 4) void pass_kernel(const Args a) {
     if (word & kWordUnsummed) atomicAdd(c + a.n_bounds + 2u, 1u);
   };
 
-  uint32_t qn = 0;  // wave-uniform: the queued rows, < 64 between steps
-  for (uint32_t tile = split; tile < pass_tiles; tile += a.splits) {  // workgroup-uniform
-    const uint64_t row0 = static_cast<uint64_t>(tile) * kPassTile + wave * (kPassPer * 64u) + lane;
-    uint32_t word[kPassPer];
-#pragma unroll
-    for (uint32_t u = 0; u < kPassPer; ++u)  // a row past the batch is clamped to its last row
-      word[u] = a.row_word[static_cast<uint32_t>(min(row0 + u * 64u, static_cast<uint64_t>(last_row)))];
-#pragma unroll
-    for (uint32_t u = 0; u < kPassPer; ++u) {
-      const uint64_t rr = row0 + u * 64u;
-      const bool mine = rr <= last_row && word[u] != kWordNone && (word[u] & kWordGroup) - g0 < nloc;
-      const uint64_t m = __ballot(mine);
-      if (m == 0) continue;  // wave-uniform
-      if (mine) q[qn + static_cast<uint32_t>(__popcll(m & ((1ull << lane) - 1ull)))] = static_cast<uint32_t>(rr);
-      qn += static_cast<uint32_t>(__popcll(m));  // <= 127 < kQueue
-      if (qn >= 64u) {
-        wave_lds_fence();
-        drain(64u);
-        const uint32_t rest = qn - 64u;  // < 64
-        const uint32_t moved = q[64u + min(lane, 63u)];
-        wave_lds_fence();
-        if (lane < rest) q[lane] = moved;
-        qn = rest;
-      }
-    }
-  }
-  wave_lds_fence();
-  drain(qn);
+  rows::pass_queue<kThreads>(
+      a.row_word, a.v.n_rows, split, a.splits, lane, wave, q,
+      [&](uint32_t word) { return word != kWordNone && (word & kWordGroup) - g0 < nloc; }, drain);
   __syncthreads();
   flush_bins(a, b_cnt, 0u, b_sum, 0u, 1u, g0, nloc, tid, kThreads);
 }
@@ -371,21 +273,6 @@ __global__ __launch_bounds__(kThreads) void finish_kernel(const Args a) {
 }  // namespace hist
 }  // namespace kacc
 
-namespace {
-
-// The table's kind, or -1 when t is not one of the eight workload tables.
-int table_kind(int t) {
-  switch (t) {
-    case KACC_T_PROC_ENERGY: case KACC_T_PROC_POWER: return KACC_KIND_PROC;
-    case KACC_T_CTR_ENERGY: case KACC_T_CTR_POWER: return KACC_KIND_CTR;
-    case KACC_T_VM_ENERGY: case KACC_T_VM_POWER: return KACC_KIND_VM;
-    case KACC_T_POD_ENERGY: case KACC_T_POD_POWER: return KACC_KIND_POD;
-    default: return -1;
-  }
-}
-
-}  // namespace
-
 extern "C" {
 
 int kacc_group_hist(kacc_ctx *ctx, kacc_table t, uint32_t zone, const kacc_top_rows *rows, const uint32_t *group,
@@ -395,10 +282,10 @@ int kacc_group_hist(kacc_ctx *ctx, kacc_table t, uint32_t zone, const kacc_top_r
   using namespace kacc::hist;
   const char *fn = "kacc_group_hist";
   if (!ctx) return KACC_EINVAL;
-  const int kind = table_kind(t);
-  if (kind < 0) return kacc_fail(ctx, KACC_EINVAL, "%s: table %d is not a workload energy / power table", fn, (int)t);
-  const uint32_t Z = ctx->cfg.zones;
-  if (zone >= Z) return kacc_fail(ctx, KACC_EINVAL, "%s: zone %u >= Z = %u", fn, zone, Z);
+  kacc::rows::Table tab;
+  Args a{};
+  int rc = kacc::rows::resolve_table(ctx, fn, t, zone, &tab);
+  if (rc != KACC_OK) return rc;
   if (!rows || !bounds) return kacc_fail(ctx, KACC_EINVAL, "%s: NULL argument", fn);
   if (n_bounds < 1 || n_bounds > KACC_HIST_MAX_BOUNDS)
     return kacc_fail(ctx, KACC_EINVAL, "%s: n_bounds %u outside 1 .. %u", fn, n_bounds, KACC_HIST_MAX_BOUNDS);
@@ -407,18 +294,13 @@ int kacc_group_hist(kacc_ctx *ctx, kacc_table t, uint32_t zone, const kacc_top_r
   if (static_cast<uint64_t>(n_groups) * (n_bounds + 1u) > KACC_HIST_MAX_BINS)
     return kacc_fail(ctx, KACC_EINVAL, "%s: %u groups x %u bins > %u", fn, n_groups, n_bounds + 1u, KACC_HIST_MAX_BINS);
   if (!group && n_groups != 1) return kacc_fail(ctx, KACC_EINVAL, "%s: NULL group with n_groups %u", fn, n_groups);
-  if (rows->n_nodes > ctx->cfg.nodes)
-    return kacc_fail(ctx, KACC_EINVAL, "%s: n_nodes %u > the context's %llu nodes", fn, rows->n_nodes,
-                     (unsigned long long)ctx->cfg.nodes);
-  if (!rows->row_off || (rows->n_rows && !rows->slot)) return kacc_fail(ctx, KACC_EINVAL, "%s: NULL row array", fn);
+  if ((rc = kacc::rows::resolve(ctx, fn, tab.kind, rows, node_mask, &a.v)) != KACC_OK) return rc;
   if (!out_bin && !out_cum && !out_sum && !out_nan && !out_unsummed)
     return kacc_fail(ctx, KACC_EINVAL, "%s: no output array", fn);
 
-  Args a{};
-  const bool power = t == KACC_T_PROC_POWER || t == KACC_T_CTR_POWER || t == KACC_T_VM_POWER || t == KACC_T_POD_POWER;
-  const bool pod = kind == KACC_KIND_POD;
+  const bool power = tab.power;
   for (uint32_t i = 0; i < n_bounds; ++i) {  // the host array is read here, before the call returns
-    a.key[i] = power ? power_key(bounds[i]) : bounds[i];
+    a.key[i] = power ? kacc::rows::power_key(bounds[i]) : bounds[i];
     if (power && a.key[i] == 0) return kacc_fail(ctx, KACC_EINVAL, "%s: bound %u is a NaN", fn, i);
     if (i && a.key[i] <= a.key[i - 1])
       return kacc_fail(ctx, KACC_EINVAL, "%s: the keys of bounds %u and %u are not strictly ascending", fn, i - 1, i);
@@ -427,24 +309,10 @@ int kacc_group_hist(kacc_ctx *ctx, kacc_table t, uint32_t zone, const kacc_top_r
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
   kacc::TimingScope timing(ctx);
 
-  a.cap = kind == KACC_KIND_PROC ? ctx->cfg.proc_slots
-          : kind == KACC_KIND_CTR ? ctx->cfg.ctr_slots
-          : kind == KACC_KIND_VM ? ctx->cfg.vm_slots
-                                 : ctx->cfg.pod_slots;
-  a.pd = kacc_derive(ctx, static_cast<kacc_kind>(pod ? KACC_KIND_PROC : kind));
-  a.derived = !pod;  // the kind's power: node_prep evaluates the guards for it
-  const int src = !power ? kEnergy : pod ? kStored : kDerived;
-  a.stride = pod ? 2 * Z : Z;
-  a.words = static_cast<const uint64_t *>(ctx->tables[t]) + zone;  // pod power: Z words into the record
+  const int src = tab.src;
+  a.words = tab.words;
   a.zone = zone;
-  a.Z = Z;
   a.n_bounds = n_bounds;
-  a.n_nodes = rows->n_nodes;
-  a.n_rows = rows->n_rows;
-  a.row_off = rows->row_off;
-  a.slot = rows->slot;
-  a.node_status = rows->node_status;
-  a.node_mask = node_mask;
   a.group = group;
   a.n_groups = n_groups;
   a.out_bin = out_bin;
@@ -479,26 +347,27 @@ int kacc_group_hist(kacc_ctx *ctx, kacc_table t, uint32_t zone, const kacc_top_r
   const uint32_t wgs = kCus * (lds == kSmallWords ? 3u : big ? 1u : 2u);
   const uint32_t tile_rows = big ? kBigThreads * kPer : kTile;
   // without a node no row is listed
-  a.tiles = a.n_nodes ? static_cast<uint32_t>((static_cast<uint64_t>(a.n_rows) + tile_rows - 1) / tile_rows) : 0u;
-  const uint32_t pass_tiles = static_cast<uint32_t>((static_cast<uint64_t>(a.n_rows) + kPassTile - 1) / kPassTile);
+  a.tiles = a.v.n_nodes ? kacc::rows::tiles_of(a.v.n_rows, tile_rows) : 0u;
+  const uint32_t pass_tiles = kacc::rows::tiles_of(a.v.n_rows, kPassTile);
   a.splits = std::max(1u, a.passes > 1 ? std::min(pass_tiles, wgs / a.passes) : std::min(a.tiles, wgs));
 
   // temporaries, stream ordered: the accumulator, for passes the sum and row words, the node flags
   const uint64_t acc_words = static_cast<uint64_t>(n_groups) * (C + 1u);
-  const uint64_t row_words = a.passes > 1 && a.tiles ? a.n_rows : 0;
+  const uint64_t row_words = a.passes > 1 && a.tiles ? a.v.n_rows : 0;
   uint64_t *tmp = nullptr;
-  KACC_HIP(ctx, hipMallocAsync(reinterpret_cast<void **>(&tmp), 8 * acc_words + 12 * row_words + 4ull * a.n_nodes, st));
+  KACC_HIP(ctx, hipMallocAsync(reinterpret_cast<void **>(&tmp), 8 * acc_words + 12 * row_words + 4ull * a.v.n_nodes, st));
   a.acc = tmp;
   a.row_fx = tmp + acc_words;
   a.row_word = reinterpret_cast<uint32_t *>(a.row_fx + row_words);
-  a.nflags = a.row_word + row_words;
-  int rc = KACC_OK;
+  a.v.nflags = a.row_word + row_words;
   if (hipMemsetAsync(a.acc, 0, 8 * acc_words, st) != hipSuccess) rc = kacc_fail(ctx, KACC_EHIP, "%s: memset", fn);
 
   if (rc == KACC_OK) {
     (void)hipGetLastError();  // clear a stale error of an earlier call
     const dim3 block(kThreads);
-    if (a.n_nodes) KACC_LAUNCH(node_prep_kernel, dim3((a.n_nodes + kThreads - 1) / kThreads), block, 0, st, a);
+    if (a.v.n_nodes)
+      KACC_LAUNCH(kacc::rows::node_prep_kernel<kThreads>, dim3((a.v.n_nodes + kThreads - 1) / kThreads), block, 0, st, a.v,
+                  a.err, kErrHist, static_cast<uint64_t *>(nullptr));
     if (a.tiles) {
       if (a.passes > 1) {
         if (src == kEnergy)

@@ -1,6 +1,5 @@
-// Internal host-side definitions shared by the engine's translation units
-// (kacc_engine.hip: interval path, kacc_join.hip: slot join + terminated
-// tracker).  Not part of the public ABI.
+// Internal host-side definitions shared by all of the engine's translation
+// units (every kacc_*.hip of the Makefile's SRC).  Not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -3,16 +3,14 @@
 // No reference counterpart: Kepler exports every running workload and leaves the cut to
 // PromQL; a fleet engine exports "every process above 1 W".  An order-preserving filter of
 // the rows of the caller's last interval batch (one workload kind): row r is selected iff
-// key(value(r)) >= key(threshold), value and key as for the top lists (kacc_top.hip), and the
-// selected rows leave in batch row order with their slot, node and Z-word energy / power
+// key(value(r)) >= key(threshold), value and key by the shared row layer (kacc_rows.hpp), and
+// the selected rows leave in batch row order with their slot, node and Z-word energy / power
 // records, dense, with per-node offsets.
 //
 // count -> scan -> scatter, no workgroup waits on another and no atomic places an item:
-//   node_prep     one thread per node: is the node listed (mask, read error, a row range inside
-//                 the batch) and, for a derived power, the guard of each zone - evaluated ONCE
-//                 per node, for the node that lists the rows - into one flag word per node
-//   count         one workgroup per tile of kTile batch rows (balanced whatever the node sizes:
-//                 the row's node is found by search in row_off).  Evaluates the predicate,
+//   node_prep     the shared layer's: one flag word per node; it also clears cnt[tiles]
+//   count         one workgroup per tile of kTile batch rows, located by the shared layer's
+//                 tile prelude (balanced whatever the node sizes).  Evaluates the predicate,
 //                 leaves one selection bit per row (a wave's ballot is the 64 rows' word) and
 //                 the tile's count
 //   scan          kacc_internal_scan_u64 over the tile counts
@@ -22,8 +20,7 @@
 //                 contiguous output range (16-B accesses for an even Z and aligned outputs)
 //   node_off      one thread per node: the items in front of the node's first row, out of the
 //                 tile offsets and the mask words
-// Every index is clamped (rows to the batch, slots to slot 0, nodes by the search's range), so
-// no load sits behind a data-dependent branch and no batch faults.
+// Every index is clamped (the shared layer's rules), so no batch faults.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -41,135 +38,57 @@ constexpr uint32_t kWords = kWaves * kPer;     // mask words per tile (<= 64: on
 constexpr uint32_t kTile = kWords * 64;        // rows per tile
 constexpr uint32_t kErrSelect = 1u << 12;      // more items than item_cap, a slot past the capacity,
                                                // a row range outside the batch
-using rows::kListed;                           // node flag word: bit z = zone z passed the guard
-
-enum Src { kEnergy = 0, kStored = 1, kDerived = 2 };  // the table of the predicate
+using rows::kDerived, rows::kEnergy, rows::kStored;  // the table of the predicate
 
 struct Args {
+  rows::View v;
   // the predicate's table
-  const uint64_t *words;  // energy / stored power words of `zone`: words[slot * stride]
-  uint32_t stride;        // Z, or 2Z for the pod records
-  ProcDerive pd;          // derived power
-  uint32_t zone, Z, derived;  // derived: the kind's power is (every kind but the pods)
-  uint64_t cap;           // the kind's slot capacity
+  const uint64_t *words;  // energy / stored power words of `zone`: words[slot * v.tab_stride]
+  uint32_t zone;
   uint64_t thr_key;
-  // the rows
-  uint32_t n_nodes, n_rows, tiles;
-  const uint32_t *row_off, *slot, *node_status, *node_mask;
+  uint32_t tiles;
   // scratch
-  uint32_t *nflags;  // [n_nodes]
   uint64_t *mask;    // [tiles * kWords] bit (r & 63) of word r / 64: row r is selected
   uint64_t *cnt;     // [tiles + 1] selected rows per tile, cnt[tiles] = 0
   uint64_t *off;     // [tiles + 1] their exclusive scan: off[tiles] = the total
-  // the records and the outputs
-  const uint64_t *tab_e, *tab_p;  // the kind's energy table; the stored power (pods) or NULL
-  uint32_t tab_stride;
+  // the outputs
   uint32_t item_cap;
   uint32_t *node_off, *out_row, *out_slot, *out_node;
   uint64_t *out_e, *out_p;
   uint32_t *err;
 };
 
-// The order rule's key of a power (header; kacc_top.hip's): NaN lowest, the zeros equal, else
-// the IEEE order.
-__host__ __device__ __forceinline__ uint64_t power_key(uint64_t b) {
-  const uint32_t hi = static_cast<uint32_t>(b >> 32), lo = static_cast<uint32_t>(b);
-  const uint32_t mag = hi & 0x7fffffffu;
-  if (mag > 0x7ff00000u || (mag == 0x7ff00000u && lo != 0)) return 0;  // NaN
-  if ((mag | lo) == 0) return 0x8000000000000000ull;                   // ±0
-  return (hi >> 31) ? ~b : (b | 0x8000000000000000ull);
-}
-
-__global__ __launch_bounds__(kThreads) void node_prep_kernel(const Args a) {
-  const uint32_t n = blockIdx.x * kThreads + threadIdx.x;
-  if (n == 0) a.cnt[a.tiles] = 0;
-  if (n >= a.n_nodes) return;
-  bool bad_range;
-  const uint32_t f = rows::node_flags(a.row_off, a.node_status, a.node_mask, a.pd, a.derived, a.Z, a.n_rows, n, bad_range);
-  if (bad_range) atomicOr(a.err, kErrSelect);  // left out
-  a.nflags[n] = f;
-}
-
-// The tile-to-node search (kacc_rows.hpp) over this call's rows.
-using rows::node_step;
-using rows::TileNodes;
-__device__ __forceinline__ TileNodes tile_nodes(const Args &a, uint32_t tile, uint32_t lane) {
-  return rows::tile_nodes(a.row_off, a.n_nodes, a.n_rows, tile, kTile, lane);
-}
-
 template <int kSrc>
 __global__ __launch_bounds__(kThreads) void count_kernel(const Args a) {
   __shared__ uint32_t s_cnt[kWaves];
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, tile = blockIdx.x;
-  const TileNodes tn = tile_nodes(a, tile, lane);
   const uint32_t word0 = wave * kPer;  // the wave's kPer consecutive words of the tile
-  const uint64_t row0 = static_cast<uint64_t>(tile) * kTile + word0 * 64u + lane;
-  const uint32_t last_row = a.n_rows - 1;
-
-  // no load sits behind a branch: a row past the batch is clamped to its last row, a bad slot
-  // to slot 0, so a lane's kPer loads of one kind are in flight together
-  bool ok[kPer];
-  uint32_t r[kPer], w[kPer], lo[kPer], hi[kPer];
+  rows::Located<kPer> t;
+  rows::locate<kPer>(a.v, nullptr, tile, kTile, lane, wave, t);
 #pragma unroll
-  for (uint32_t u = 0; u < kPer; ++u) {
-    const uint64_t rr = row0 + u * 64u;
-    ok[u] = rr <= last_row;
-    r[u] = static_cast<uint32_t>(min(rr, static_cast<uint64_t>(last_row)));
-    w[u] = a.slot[r[u]];
-    lo[u] = tn.first;
-    hi[u] = tn.last;
-  }
-  for (uint32_t s = 0; s < tn.steps; ++s) {  // workgroup-uniform
-#pragma unroll
-    for (uint32_t u = 0; u < kPer; ++u) node_step(a.row_off, r[u], lo[u], hi[u]);
-  }
-  uint32_t f[kPer];
-#pragma unroll
-  for (uint32_t u = 0; u < kPer; ++u) {
-    const uint32_t n = lo[u];
-    const uint32_t r0 = a.row_off[n], r1 = a.row_off[n + 1];
-    f[u] = a.nflags[n];
-    ok[u] = ok[u] && r0 <= r[u] && r[u] < r1 && (f[u] & kListed);
-  }
-  bool bad = false;
+  for (uint32_t u = 0; u < kPer; ++u) rows::check_row(a.v, 1u, t, u);
   uint32_t c = 0;
 #pragma unroll
   for (uint32_t u = 0; u < kPer; ++u) {
-    const uint64_t sl = w[u] & KACC_SLOT_MASK;
-    const bool in = sl < a.cap;
-    bad = bad || (ok[u] && !in);  // left out
-    ok[u] = ok[u] && in;
     uint64_t v = 0;
-    if (a.cap != 0) {  // uniform
-      if constexpr (kSrc == kDerived) {
-        const double ratio = a.pd.ratio[in ? sl : 0];
-        const double aP = a.pd.active_power[static_cast<uint64_t>(lo[u]) * a.Z + a.zone];
-        v = static_cast<uint64_t>(__double_as_longlong(((f[u] >> a.zone) & 1u) ? ratio * aP : 0.0));
-      } else {
-        v = a.words[(in ? sl : 0) * a.stride];
-      }
-    }
-    const uint64_t key = kSrc == kEnergy ? v : power_key(v);
-    const uint64_t m = __ballot(ok[u] && key >= a.thr_key);
+    if (a.v.cap != 0)  // uniform
+      v = rows::value_bits<kSrc>(a.words, a.v.tab_stride, a.v.pd, a.v.Z, a.zone, t.sl[u], t.node[u], t.f[u]);
+    const uint64_t key = kSrc == kEnergy ? v : rows::power_key(v);
+    const uint64_t m = __ballot(t.ok[u] && key >= a.thr_key);
     if (lane == 0) a.mask[static_cast<uint64_t>(tile) * kWords + word0 + u] = m;
     c += static_cast<uint32_t>(__popcll(m));
   }
-  if (bad) atomicOr(a.err, kErrSelect);
+  if (t.bad) atomicOr(a.err, kErrSelect);  // left out
   if (lane == 0) s_cnt[wave] = c;
   __syncthreads();
   if (tid == 0) {
-    uint32_t t = 0;
-    for (uint32_t i = 0; i < kWaves; ++i) t += s_cnt[i];
-    a.cnt[tile] = t;
+    uint32_t sum = 0;
+    for (uint32_t i = 0; i < kWaves; ++i) sum += s_cnt[i];
+    a.cnt[tile] = sum;
   }
 }
 
 using u64x2 = __attribute__((ext_vector_type(2))) unsigned long long;
-__device__ __forceinline__ void wave_lds_fence() {  // a wave's LDS writes before its reads (kacc_top.hip's)
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // kDer: the power is derived (ratio[slot] · ActivePower[node], the node's guard flag), else the
 // stored record.  kW: words per lane and copy (2: 16-B loads and stores; an even Z, aligned outputs).
@@ -177,7 +96,8 @@ template <bool kDer, uint32_t kW>
 __global__ __launch_bounds__(kThreads) void scatter_kernel(const Args a) {
   __shared__ uint32_t s_slot[kWaves][64], s_node[kWaves][64];
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, tile = blockIdx.x;
-  const uint32_t Z = a.Z;
+  const rows::View &v = a.v;
+  const uint32_t Z = v.Z;
   const uint64_t limit = min(a.off[a.tiles], static_cast<uint64_t>(a.item_cap));
   const uint64_t tbase = a.off[tile];
   if (tbase >= limit) return;  // workgroup-uniform: nothing of this tile fits (or it is empty and last)
@@ -191,8 +111,8 @@ __global__ __launch_bounds__(kThreads) void scatter_kernel(const Args a) {
     inc += lane >= d ? t : 0u;
   }
   const uint32_t excl = inc - pc;
-  const TileNodes tn = tile_nodes(a, tile, lane);
-  const uint32_t last_row = a.n_rows - 1;
+  const rows::TileNodes tn = rows::tile_nodes(v.row_off, v.n_nodes, v.n_rows, tile, kTile, lane);
+  const uint32_t last_row = v.n_rows - 1;
 
   for (uint32_t u = 0; u < kPer; ++u) {
     const uint32_t j = wave * kPer + u;
@@ -202,10 +122,10 @@ __global__ __launch_bounds__(kThreads) void scatter_kernel(const Args a) {
     if (c == 0 || base >= limit) continue;  // wave-uniform
     const uint64_t rr = static_cast<uint64_t>(tile) * kTile + j * 64u + lane;
     const uint32_t r = static_cast<uint32_t>(min(rr, static_cast<uint64_t>(last_row)));
-    const uint32_t sw = a.slot[r] & KACC_SLOT_MASK;
-    const uint32_t sl = sw < a.cap ? sw : 0u;  // a selected row's slot is below the capacity (the count pass)
+    const uint32_t sw = v.slot[r] & KACC_SLOT_MASK;
+    const uint32_t sl = sw < v.cap ? sw : 0u;  // a selected row's slot is below the capacity (the count pass)
     uint32_t lo = tn.first, hi = tn.last;
-    for (uint32_t s = 0; s < tn.steps; ++s) node_step(a.row_off, r, lo, hi);
+    for (uint32_t s = 0; s < tn.steps; ++s) rows::node_step(v.row_off, r, lo, hi);
     const bool sel = (m >> lane) & 1ull;
     const uint32_t rank = static_cast<uint32_t>(__popcll(m & ((1ull << lane) - 1ull)));
     const uint64_t i = base + rank;
@@ -218,7 +138,7 @@ __global__ __launch_bounds__(kThreads) void scatter_kernel(const Args a) {
         if (a.out_node) a.out_node[i] = lo;
       }
     }
-    wave_lds_fence();
+    rows::wave_lds_fence();
     // the c items' records are one contiguous output range of c Z words: lane l takes words
     // kW (64 k + l) .. + kW, each word's slot and node from its item's entry
     const uint32_t words = static_cast<uint32_t>(min(static_cast<uint64_t>(c), limit - base)) * Z;
@@ -231,7 +151,7 @@ __global__ __launch_bounds__(kThreads) void scatter_kernel(const Args a) {
       const uint64_t s = s_slot[wave][it];
       const uint64_t nd = s_node[wave][it];
       if (a.out_e) {
-        const uint64_t *src = a.tab_e + s * a.tab_stride + z;
+        const uint64_t *src = v.tab_e + s * v.tab_stride + z;
         if constexpr (kW == 2) {
           const u64x2 e = *reinterpret_cast<const u64x2 *>(src);
           if (valid) *reinterpret_cast<u64x2 *>(a.out_e + o0 + wd) = e;
@@ -243,9 +163,9 @@ __global__ __launch_bounds__(kThreads) void scatter_kernel(const Args a) {
       if (a.out_p) {
         uint64_t p[kW];
         if constexpr (kDer) {
-          const double ratio = a.pd.ratio[s];
-          const uint32_t f = a.nflags[nd];
-          const double *aP = a.pd.active_power + nd * Z + z;
+          const double ratio = v.pd.ratio[s];
+          const uint32_t f = v.nflags[nd];
+          const double *aP = v.pd.active_power + nd * Z + z;
           double ap[kW];
           if constexpr (kW == 2) {
             const u64x2 t = *reinterpret_cast<const u64x2 *>(aP);
@@ -256,9 +176,9 @@ __global__ __launch_bounds__(kThreads) void scatter_kernel(const Args a) {
           }
 #pragma unroll
           for (uint32_t q = 0; q < kW; ++q)
-            p[q] = static_cast<uint64_t>(__double_as_longlong(((f >> (z + q)) & 1u) ? ratio * ap[q] : 0.0));
+            p[q] = rows::derived_bits(f, z + q, ratio, ap[q]);
         } else {
-          const uint64_t *src = a.tab_p + s * a.tab_stride + z;
+          const uint64_t *src = v.tab_p + s * v.tab_stride + z;
           if constexpr (kW == 2) {
             const u64x2 t = *reinterpret_cast<const u64x2 *>(src);
             p[0] = t.x;
@@ -279,7 +199,7 @@ __global__ __launch_bounds__(kThreads) void scatter_kernel(const Args a) {
         }
       }
     }
-    wave_lds_fence();  // the next word's entries overwrite these
+    rows::wave_lds_fence();  // the next word's entries overwrite these
   }
 }
 
@@ -289,11 +209,11 @@ __global__ __launch_bounds__(kThreads) void node_off_kernel(const Args a) {
   const uint64_t total = a.off[a.tiles];
   // item_cap 0 is the sizing call
   if (n == 0 && total > a.item_cap && a.item_cap) atomicOr(a.err, kErrSelect);
-  if (n > a.n_nodes) return;
+  if (n > a.v.n_nodes) return;
   uint64_t pos = total;
   if (a.tiles) {  // uniform
-    const uint32_t r = min(a.row_off[min(n, a.n_nodes)], a.n_rows);  // n = n_nodes: the batch's end
-    const uint32_t rc = min(r, a.n_rows - 1);
+    const uint32_t r = min(a.v.row_off[min(n, a.v.n_nodes)], a.v.n_rows);  // n = n_nodes: the batch's end
+    const uint32_t rc = min(r, a.v.n_rows - 1);
     const uint32_t tile = rc / kTile, j = (rc % kTile) / 64u, b = rc & 63u;
     uint64_t p = a.off[tile];
 #pragma unroll 8
@@ -302,28 +222,13 @@ __global__ __launch_bounds__(kThreads) void node_off_kernel(const Args a) {
       const uint64_t take = i < j ? ~0ull : (i == j ? (1ull << b) - 1ull : 0ull);
       p += static_cast<uint32_t>(__popcll(m & take));
     }
-    pos = r < a.n_rows ? p : total;
+    pos = r < a.v.n_rows ? p : total;
   }
   a.node_off[n] = static_cast<uint32_t>(pos);  // <= n_rows
 }
 
 }  // namespace sel
 }  // namespace kacc
-
-namespace {
-
-// The table's kind, or -1 when t is not one of the eight workload tables.
-int table_kind(int t) {
-  switch (t) {
-    case KACC_T_PROC_ENERGY: case KACC_T_PROC_POWER: return KACC_KIND_PROC;
-    case KACC_T_CTR_ENERGY: case KACC_T_CTR_POWER: return KACC_KIND_CTR;
-    case KACC_T_VM_ENERGY: case KACC_T_VM_POWER: return KACC_KIND_VM;
-    case KACC_T_POD_ENERGY: case KACC_T_POD_POWER: return KACC_KIND_POD;
-    default: return -1;
-  }
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -334,15 +239,12 @@ int kacc_select_above(kacc_ctx *ctx, kacc_table t, uint32_t zone, uint64_t thres
   using namespace kacc::sel;
   const char *fn = "kacc_select_above";
   if (!ctx) return KACC_EINVAL;
-  const int kind = table_kind(t);
-  if (kind < 0) return kacc_fail(ctx, KACC_EINVAL, "%s: table %d is not a workload energy / power table", fn, (int)t);
-  const uint32_t Z = ctx->cfg.zones;
-  if (zone >= Z) return kacc_fail(ctx, KACC_EINVAL, "%s: zone %u >= Z = %u", fn, zone, Z);
+  kacc::rows::Table tab;
+  Args a{};
+  int rc = kacc::rows::resolve_table(ctx, fn, t, zone, &tab);
+  if (rc != KACC_OK) return rc;
   if (!rows || !node_off) return kacc_fail(ctx, KACC_EINVAL, "%s: NULL argument", fn);
-  if (rows->n_nodes > ctx->cfg.nodes)
-    return kacc_fail(ctx, KACC_EINVAL, "%s: n_nodes %u > the context's %llu nodes", fn, rows->n_nodes,
-                     (unsigned long long)ctx->cfg.nodes);
-  if (!rows->row_off || (rows->n_rows && !rows->slot)) return kacc_fail(ctx, KACC_EINVAL, "%s: NULL row array", fn);
+  if ((rc = kacc::rows::resolve(ctx, fn, tab.kind, rows, node_mask, &a.v)) != KACC_OK) return rc;
   if (item_cap && !out_row && !out_slot && !out_node && !out_energy && !out_power)
     return kacc_fail(ctx, KACC_EINVAL, "%s: item_cap %u and no output array", fn, item_cap);
   KACC_HIP(ctx, hipSetDevice(ctx->device));
@@ -353,32 +255,11 @@ int kacc_select_above(kacc_ctx *ctx, kacc_table t, uint32_t zone, uint64_t thres
   }
   kacc::TimingScope timing(ctx);
 
-  Args a{};
-  const bool power = t == KACC_T_PROC_POWER || t == KACC_T_CTR_POWER || t == KACC_T_VM_POWER || t == KACC_T_POD_POWER;
-  const bool pod = kind == KACC_KIND_POD;
-  const int te = pod ? KACC_T_POD_ENERGY : kind == KACC_KIND_PROC ? KACC_T_PROC_ENERGY
-                 : kind == KACC_KIND_CTR ? KACC_T_CTR_ENERGY : KACC_T_VM_ENERGY;
-  a.cap = kind == KACC_KIND_PROC ? ctx->cfg.proc_slots
-          : kind == KACC_KIND_CTR ? ctx->cfg.ctr_slots
-          : kind == KACC_KIND_VM ? ctx->cfg.vm_slots
-                                 : ctx->cfg.pod_slots;
-  a.pd = kacc_derive(ctx, static_cast<kacc_kind>(pod ? KACC_KIND_PROC : kind));
-  a.derived = !pod;  // the kind's power, whichever table the predicate reads
-  const bool pred_derived = power && !pod;
-  a.tab_stride = a.stride = pod ? 2 * Z : Z;
-  a.words = static_cast<const uint64_t *>(ctx->tables[t]) + zone;  // pod power: Z words into the record
-  a.tab_e = static_cast<const uint64_t *>(ctx->tables[te]);
-  a.tab_p = pod ? static_cast<const uint64_t *>(ctx->tables[KACC_T_POD_POWER]) : nullptr;
+  const uint32_t Z = a.v.Z;
+  a.words = tab.words;
   a.zone = zone;
-  a.Z = Z;
-  a.thr_key = power ? power_key(threshold) : threshold;  // NaN: 0, every listed row
-  a.n_nodes = rows->n_nodes;
-  a.n_rows = rows->n_rows;
-  a.tiles = static_cast<uint32_t>((static_cast<uint64_t>(a.n_rows) + kTile - 1) / kTile);
-  a.row_off = rows->row_off;
-  a.slot = rows->slot;
-  a.node_status = rows->node_status;
-  a.node_mask = node_mask;
+  a.thr_key = tab.power ? kacc::rows::power_key(threshold) : threshold;  // NaN: 0, every listed row
+  a.tiles = kacc::rows::tiles_of(a.v.n_rows, kTile);
   a.item_cap = item_cap;
   a.node_off = node_off;
   a.out_row = out_row;
@@ -392,33 +273,33 @@ int kacc_select_above(kacc_ctx *ctx, kacc_table t, uint32_t zone, uint64_t thres
   const uint64_t n = a.tiles + 1ull, scan_tiles = kacc_internal_scan_tiles(n);
   const uint64_t mask_words = static_cast<uint64_t>(a.tiles) * kWords;
   uint64_t *tmp = nullptr;
-  KACC_HIP(ctx, hipMallocAsync(reinterpret_cast<void **>(&tmp), 8 * (mask_words + 2 * n + scan_tiles) + 4ull * a.n_nodes, st));
+  KACC_HIP(ctx, hipMallocAsync(reinterpret_cast<void **>(&tmp), 8 * (mask_words + 2 * n + scan_tiles) + 4ull * a.v.n_nodes, st));
   a.mask = tmp;
   a.cnt = tmp + mask_words;
   a.off = a.cnt + n;
   uint64_t *tile_sum = a.off + n;
-  a.nflags = reinterpret_cast<uint32_t *>(tile_sum + scan_tiles);
+  a.v.nflags = reinterpret_cast<uint32_t *>(tile_sum + scan_tiles);
 
   (void)hipGetLastError();  // clear a stale error of an earlier call
-  const dim3 node_grid(static_cast<uint32_t>((a.n_nodes + 1ull + kThreads - 1) / kThreads)), block(kThreads);
-  KACC_LAUNCH(node_prep_kernel, node_grid, block, 0, st, a);
+  const dim3 node_grid(static_cast<uint32_t>((a.v.n_nodes + 1ull + kThreads - 1) / kThreads)), block(kThreads);
+  KACC_LAUNCH(kacc::rows::node_prep_kernel<kThreads>, node_grid, block, 0, st, a.v, a.err, kErrSelect, a.cnt + a.tiles);
   if (a.tiles) {
-    if (pred_derived)
+    if (tab.src == kDerived)
       KACC_LAUNCH(count_kernel<kDerived>, dim3(a.tiles), block, 0, st, a);
-    else if (power)
+    else if (tab.src == kStored)
       KACC_LAUNCH(count_kernel<kStored>, dim3(a.tiles), block, 0, st, a);
     else
       KACC_LAUNCH(count_kernel<kEnergy>, dim3(a.tiles), block, 0, st, a);
   }
-  int rc = kacc_internal_scan_u64(ctx, a.cnt, n, tile_sum, a.off, st);
+  rc = kacc_internal_scan_u64(ctx, a.cnt, n, tile_sum, a.off, st);
   if (rc == KACC_OK) {
     if (a.tiles && item_cap) {
       // 16-B copies for an even Z when the caller's arrays allow them (the tables are hipMalloc'ed)
       const bool wide = Z % 2 == 0 &&
                         ((reinterpret_cast<uintptr_t>(out_energy) | reinterpret_cast<uintptr_t>(out_power)) & 15u) == 0;
-      if (a.derived && wide)
+      if (a.v.derived && wide)
         KACC_LAUNCH((scatter_kernel<true, 2>), dim3(a.tiles), block, 0, st, a);
-      else if (a.derived)
+      else if (a.v.derived)
         KACC_LAUNCH((scatter_kernel<true, 1>), dim3(a.tiles), block, 0, st, a);
       else if (wide)
         KACC_LAUNCH((scatter_kernel<false, 2>), dim3(a.tiles), block, 0, st, a);

@@ -5,10 +5,11 @@
 // The rows are those of the caller's last interval batch (one workload kind);
 // the value of a row is its slot's element of the table in `zone`: an energy
 // word, a stored pod power, or the derived power ratio[slot] · ActivePower[node]
-// under the guard of kacc_derive.hpp.  A segment knows its node, so the guard
-// operands are loaded once per node and KACC_T_*_NODE is not gathered (the same
-// bits for rows of the node's last processed interval: the validity rule of the
-// derived tables).
+// under the guard of kacc_derive.hpp.  The rows' view, the order rule's key and the
+// host's resolver are the shared row layer's (kacc_rows.hpp); the value path is this
+// file's own: a segment knows its node, so the guard operands are loaded once per
+// node into LDS and KACC_T_*_NODE is not gathered (the same bits for rows of the
+// node's last processed interval: the validity rule of the derived tables).
 //
 // Order (the header's rule): descending key, equal keys in ascending batch row
 // order.  The kernels sort ascending by (~key, row): three 32-bit compares, no
@@ -33,6 +34,7 @@
 
 #include "kacc_derive.hpp"
 #include "kacc_internal.hpp"
+#include "kacc_rows.hpp"
 
 namespace kacc {
 namespace top {
@@ -44,7 +46,8 @@ constexpr uint32_t kMinFan = 8;        // candidate lists per workgroup in stage
 constexpr uint32_t kErrTop = 1u << 9;  // a slot past the capacity or a row range outside the batch
 constexpr uint32_t kNone = 0xffffffffu;
 
-enum Src { kEnergy = 0, kStored = 1, kDerived = 2, kCand = 3 };  // where entries come from
+using rows::kDerived, rows::kEnergy, rows::kStored, rows::power_key;  // where entries come from: a table,
+constexpr int kCand = 3;                                               // or candidate lists
 enum Out { kNodes = 0, kList = 1, kFleet = 2 };                   // where the kept entries go
 // Threads per workgroup.  A node's selection is one dependent chain (loads, sort, loads), so the
 // per-node lists pay in workgroups per CU: six of 256 threads (their LDS) against four of 512.
@@ -59,16 +62,11 @@ struct Cand {  // candidate lists: list l holds count[l] <= k entries at [l * k,
 };
 
 struct Args {
+  rows::View v;  // the rows (no node mask, no flag words: the guard operands go through LDS)
   // the table
-  const uint64_t *words;  // energy / stored power words of `zone`: words[slot * stride]
-  uint32_t stride;        // Z, or 2Z for the pod records
+  const uint64_t *words;  // energy / stored power words of `zone`: words[slot * v.tab_stride]
   uint32_t mode;          // Src of the table (the value of an emitted entry)
-  ProcDerive pd;          // derived power
   uint32_t zone;
-  uint64_t cap;           // the kind's slot capacity
-  // the rows
-  uint32_t n_nodes, n_rows;
-  const uint32_t *row_off, *slot, *node_status;
   // selection
   uint32_t k;
   uint32_t group;    // sources (nodes or lists) per workgroup
@@ -78,15 +76,6 @@ struct Args {
   uint64_t *out_value;
   uint32_t *err;
 };
-
-// The order rule's key of a power (header): NaN lowest, the zeros equal, else the IEEE order.
-__device__ __forceinline__ uint64_t power_key(uint64_t b) {
-  const uint32_t hi = static_cast<uint32_t>(b >> 32), lo = static_cast<uint32_t>(b);
-  const uint32_t mag = hi & 0x7fffffffu;
-  if (mag > 0x7ff00000u || (mag == 0x7ff00000u && lo != 0)) return 0;  // NaN
-  if ((mag | lo) == 0) return 0x8000000000000000ull;                   // ±0
-  return (hi >> 31) ? ~b : (b | 0x8000000000000000ull);
-}
 
 struct NodeGuard {  // the node's operands of the guard (process.go:124), loaded once per node
   double aP;
@@ -104,9 +93,9 @@ __device__ __forceinline__ NodeGuard node_guard(const ProcDerive &d, uint32_t n,
 template <int kSrc>
 __device__ __forceinline__ uint64_t slot_value(const Args &a, uint64_t s, const NodeGuard &g) {
   if constexpr (kSrc == kDerived) {
-    return static_cast<uint64_t>(__double_as_longlong(g.live ? a.pd.ratio[s] * g.aP : 0.0));
+    return static_cast<uint64_t>(__double_as_longlong(g.live ? a.v.pd.ratio[s] * g.aP : 0.0));
   } else {
-    return a.words[s * a.stride];
+    return a.words[s * a.v.tab_stride];
   }
 }
 
@@ -171,9 +160,7 @@ __global__ __launch_bounds__(threads_of(kOut)) void select_kernel(const Args a) 
         if (st > 64 || next > 64) {
           __syncthreads();
         } else {
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          __builtin_amdgcn_wave_barrier();
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+          rows::wave_lds_fence();
         }
       }
     }
@@ -212,7 +199,7 @@ __global__ __launch_bounds__(threads_of(kOut)) void select_kernel(const Args a) 
   __shared__ uint32_t s_pre[kGroup + 1], s_r0[kGroup];
   __shared__ double s_aP[kGroup];
   __shared__ uint32_t s_live[kGroup];
-  const uint32_t n_src = kSrc == kCand ? a.n_lists : a.n_nodes;
+  const uint32_t n_src = kSrc == kCand ? a.n_lists : a.v.n_nodes;
   const uint32_t src0 = static_cast<uint32_t>(min(static_cast<uint64_t>(blockIdx.x) * a.group, static_cast<uint64_t>(n_src)));
   const uint32_t ng = min(a.group, n_src - src0);
   uint32_t total;
@@ -221,12 +208,12 @@ __global__ __launch_bounds__(threads_of(kOut)) void select_kernel(const Args a) 
   } else {
     if (tid < ng) {  // ng <= kGroup; every load issued before the first use: one round trip
       const uint32_t n = src0 + tid;
-      const uint32_t r0 = a.row_off[n], r1 = a.row_off[n + 1];
-      const uint32_t status = a.node_status ? a.node_status[n] : 0u;
+      const uint32_t r0 = a.v.row_off[n], r1 = a.v.row_off[n + 1];
+      const uint32_t status = a.v.node_status ? a.v.node_status[n] : 0u;
       NodeGuard g{0.0, false};
-      if constexpr (kSrc == kDerived) g = node_guard(a.pd, n, a.zone);
+      if constexpr (kSrc == kDerived) g = node_guard(a.v.pd, n, a.zone);
       uint32_t cnt = 0;
-      if (r0 > r1 || r1 > a.n_rows)
+      if (r0 > r1 || r1 > a.v.n_rows)
         atomicOr(a.err, kErrTop);  // left out
       else if (!(status & KACC_NODE_READ_ERROR))
         cnt = r1 - r0;
@@ -294,22 +281,22 @@ __global__ __launch_bounds__(threads_of(kOut)) void select_kernel(const Args a) 
         ln[u] = n;
         row[u] = s_r0[n] + (f - s_pre[n]);
         node[u] = src0 + n;
-        w[u] = a.slot[row[u]];
+        w[u] = a.v.slot[row[u]];
       }
       uint64_t v[kPer];
       bool bad = false;
 #pragma unroll
       for (uint32_t u = 0; u < kPer; ++u) {
         const uint64_t sl = w[u] & KACC_SLOT_MASK;
-        const bool in = sl < a.cap;
+        const bool in = sl < a.v.cap;
         bad = bad || (ok[u] && !in);  // left out
         ok[u] = ok[u] && in;
         v[u] = 0;
-        if (a.cap != 0) {  // uniform
+        if (a.v.cap != 0) {  // uniform
           if constexpr (kSrc == kDerived)
-            v[u] = static_cast<uint64_t>(__double_as_longlong(a.pd.ratio[in ? sl : 0]));
+            v[u] = static_cast<uint64_t>(__double_as_longlong(a.v.pd.ratio[in ? sl : 0]));
           else
-            v[u] = a.words[(in ? sl : 0) * a.stride];
+            v[u] = a.words[(in ? sl : 0) * a.v.tab_stride];
         }
       }
       if (bad) atomicOr(a.err, kErrTop);
@@ -356,11 +343,11 @@ __global__ __launch_bounds__(threads_of(kOut)) void select_kernel(const Args a) 
       if (j < count) {
         row = s_row[j];
         node = kOut == kFleet ? s_node[j] : blockIdx.x;
-        sl = a.slot[row] & KACC_SLOT_MASK;  // < cap: checked when the row entered
+        sl = a.v.slot[row] & KACC_SLOT_MASK;  // < cap: checked when the row entered
         if (a.mode == kDerived)
-          v = slot_value<kDerived>(a, sl, node_guard(a.pd, node, a.zone));
+          v = slot_value<kDerived>(a, sl, node_guard(a.v.pd, node, a.zone));
         else
-          v = a.words[static_cast<uint64_t>(sl) * a.stride];
+          v = a.words[static_cast<uint64_t>(sl) * a.v.tab_stride];
       }
       a.out_row[o + j] = row;
       if (a.out_slot) a.out_slot[o + j] = sl;
@@ -377,49 +364,18 @@ namespace {
 
 using kacc::top::Args;
 
-// The table's kind, or -1 when t is not one of the eight workload tables.
-int table_kind(int t) {
-  switch (t) {
-    case KACC_T_PROC_ENERGY: case KACC_T_PROC_POWER: return KACC_KIND_PROC;
-    case KACC_T_CTR_ENERGY: case KACC_T_CTR_POWER: return KACC_KIND_CTR;
-    case KACC_T_VM_ENERGY: case KACC_T_VM_POWER: return KACC_KIND_VM;
-    case KACC_T_POD_ENERGY: case KACC_T_POD_POWER: return KACC_KIND_POD;
-    default: return -1;
-  }
-}
-
 int fill_args(kacc_ctx *ctx, const char *fn, kacc_table t, uint32_t zone, uint32_t k, const kacc_top_rows *rows,
               const void *out_count, const void *out_row, Args *a) {
-  const int kind = table_kind(t);
-  if (kind < 0) return kacc_fail(ctx, KACC_EINVAL, "%s: table %d is not a workload energy / power table", fn, (int)t);
-  const uint32_t Z = ctx->cfg.zones;
-  if (zone >= Z) return kacc_fail(ctx, KACC_EINVAL, "%s: zone %u >= Z = %u", fn, zone, Z);
+  kacc::rows::Table tab;
+  *a = Args{};
+  int rc = kacc::rows::resolve_table(ctx, fn, t, zone, &tab);
+  if (rc != KACC_OK) return rc;
   if (k < 1 || k > KACC_TOP_MAX) return kacc_fail(ctx, KACC_EINVAL, "%s: k = %u outside 1 .. %u", fn, k, KACC_TOP_MAX);
   if (!rows || !out_count || !out_row) return kacc_fail(ctx, KACC_EINVAL, "%s: NULL argument", fn);
-  if (rows->n_nodes > ctx->cfg.nodes)
-    return kacc_fail(ctx, KACC_EINVAL, "%s: n_nodes %u > the context's %llu nodes", fn, rows->n_nodes,
-                     (unsigned long long)ctx->cfg.nodes);
-  if (!rows->row_off || (rows->n_rows && !rows->slot)) return kacc_fail(ctx, KACC_EINVAL, "%s: NULL row array", fn);
-  *a = Args{};
-  a->cap = kind == KACC_KIND_PROC ? ctx->cfg.proc_slots
-           : kind == KACC_KIND_CTR ? ctx->cfg.ctr_slots
-           : kind == KACC_KIND_VM ? ctx->cfg.vm_slots
-                                  : ctx->cfg.pod_slots;
-  a->pd = kacc_derive(ctx, static_cast<kacc_kind>(kind == KACC_KIND_POD ? KACC_KIND_PROC : kind));
-  if (kacc_derived_kind(t) >= 0) {
-    a->mode = kacc::top::kDerived;
-  } else {
-    const bool power = t == KACC_T_POD_POWER;
-    a->mode = power ? kacc::top::kStored : kacc::top::kEnergy;
-    a->words = static_cast<const uint64_t *>(ctx->tables[t]) + zone;  // pod power: Z words into the record
-    a->stride = kind == KACC_KIND_POD ? 2 * Z : Z;
-  }
+  if ((rc = kacc::rows::resolve(ctx, fn, tab.kind, rows, nullptr, &a->v)) != KACC_OK) return rc;
+  a->mode = tab.src;
+  a->words = tab.words;
   a->zone = zone;
-  a->n_nodes = rows->n_nodes;
-  a->n_rows = rows->n_rows;
-  a->row_off = rows->row_off;
-  a->slot = rows->slot;
-  a->node_status = rows->node_status;
   a->k = k;
   a->err = ctx->d_err;
   return KACC_OK;
@@ -445,8 +401,8 @@ int kacc_top_nodes(kacc_ctx *ctx, kacc_table t, uint32_t zone, uint32_t k, const
   Args a;
   const int rc = fill_args(ctx, "kacc_top_nodes", t, zone, k, rows, out_count, out_row, &a);
   if (rc != KACC_OK) return rc;
-  if (a.n_nodes == 0) return KACC_OK;
-  if (a.n_nodes > 0x7fffffffu) return kacc_fail(ctx, KACC_EINVAL, "kacc_top_nodes: too many nodes for one launch");
+  if (a.v.n_nodes == 0) return KACC_OK;
+  if (a.v.n_nodes > 0x7fffffffu) return kacc_fail(ctx, KACC_EINVAL, "kacc_top_nodes: too many nodes for one launch");
   KACC_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
   kacc::TimingScope timing(ctx);
@@ -456,7 +412,7 @@ int kacc_top_nodes(kacc_ctx *ctx, kacc_table t, uint32_t zone, uint32_t k, const
   a.out_slot = out_slot;
   a.out_value = out_value;
   (void)hipGetLastError();
-  launch_rows<kacc::top::kNodes>(a, a.n_nodes, st);
+  launch_rows<kacc::top::kNodes>(a, a.v.n_nodes, st);
   KACC_HIP(ctx, hipGetLastError());
   return KACC_OK;
 }
@@ -474,7 +430,7 @@ int kacc_top_fleet(kacc_ctx *ctx, kacc_table t, uint32_t zone, uint32_t k, const
   kacc::TimingScope timing(ctx);
   // stage 1 leaves L1 lists in A; the passes of stage 2 alternate between B and A
   const uint32_t fan = std::max(kMinFan, (2 * kBuf + k - 1) / k);  // >= 4096 candidates per workgroup
-  const uint64_t L1 = (static_cast<uint64_t>(a.n_nodes) + kGroup - 1) / kGroup;
+  const uint64_t L1 = (static_cast<uint64_t>(a.v.n_nodes) + kGroup - 1) / kGroup;
   const uint64_t L2 = (L1 + fan - 1) / fan;
   const uint64_t ents = (L1 + L2) * k, lists = L1 + L2;
   char *tmp = nullptr;
