@@ -761,13 +761,42 @@ int kacc_unpack(kacc_ctx *ctx, kacc_kind kind, uint32_t n, const uint32_t *slot_
  *
  * kacc_tracker_add() takes one interval's terminated workloads — the per-node
  * segments of kacc_slot_join — and reads their final values from the kind's
- * state tables (the slots are not reused before the next join).  A node's
- * batch is added as Go's loop over procs.Terminated (process.go:89-99) would
- * add it in the map order "descending target-zone energy, then slot"; Go's
- * map order is unspecified, and for any batch whose energies differ at the
- * retention boundary the retained set is the same for every order.  Ties at
- * the boundary keep items already tracked first (Go's heap requires a strictly
- * higher energy to evict), then the batch order.  Tracked items are frozen
+ * state tables (the slots are not reused before the next join).
+ *
+ * THE RULE.  A node's set is ordered by target-zone energy descending, items
+ * of equal energy in the order they were admitted.  One add drops the
+ * candidates already tracked and those below min_energy, orders the rest by
+ * energy descending, then position in the node's terminated list (= slot: the
+ * join lists them ascending by slot), places them BEHIND the tracked items of
+ * equal energy, and cuts the set to max_size.  So ties at the retention
+ * boundary keep items already tracked first, then the earlier list positions.
+ * kacc_tracker_items / kacc_tracker_read return a node's items in this order.
+ *
+ * WHAT THAT IS IN GO.  Go's loop over procs.Terminated (process.go:89-99)
+ * runs in an unspecified map order.  Where no item is dropped at the energy
+ * of the last item kept, every order — and the rule — keeps the same items.
+ * With ties at that boundary the retained TARGET-ZONE ENERGIES are still
+ * what every Go order keeps (the max_size highest, as a multiset), but WHICH
+ * of the tied IDs stay is the rule's own, deterministic choice and can differ
+ * from Go's heap.  Example: max_size 2 and three single-item adds, key 101
+ * (5 µJ), 102 (5 µJ), 103 (9 µJ): Go pops its heap's root for 103, the older
+ * of the tied minima, and keeps {102, 103}; the rule cuts the item it ranks
+ * last, the newer one, and keeps {101, 103}.  The three arrive in different
+ * intervals, so no map order reconciles the two; Go's own choice among tied
+ * items depends on its heap's layout (which minimum happens to be the root).
+ * tests/tracker_ref.py states the rule; tests/test_tracker_ref.py holds the
+ * example and the comparison with the Go heap.
+ *
+ * The already-tracked check (:90) is made against the set as it stands when
+ * the candidate's chunk of the list starts (64 candidates per chunk): a key
+ * listed again is ignored while its tracked copy survives.  When that copy is
+ * evicted by an earlier chunk of the same add, the new copy is a candidate
+ * like any other — as in Go, where it depends on the map order whether the
+ * old copy is still tracked when the new one arrives.  The join lists a key
+ * once per add and only after it left the running set, so this needs a key
+ * that terminates twice.
+ *
+ * Tracked items are frozen
  * copies (energy and power per zone), as Add(prev.Clone()) keeps.  Nodes are
  * those of the context (kacc_config.nodes): the device holds, PER NODE,
  * max_size items (capacity for an unlimited tracker), i.e.

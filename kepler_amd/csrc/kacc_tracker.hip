@@ -11,16 +11,29 @@
 // engine keeps one bounded set PER NODE — the top max_size of that node
 // only — never a fleet-wide top-N.
 //
-// One interval's batch (the slot join's per-node terminated segments, values
-// read from the kind's state tables) is added as Go would add it in the map
-// order "descending target-zone energy, then slot".  In that order a node's
-// heap keeps the max_size best of (tracked ∪ batch), ties at the boundary
-// going to tracked items first (eviction needs a strictly higher energy) and
-// then to the batch order.  Each node's set is kept sorted (energy desc, then
-// insertion order), so one add is, per node (one wavefront each):
+// One interval's batch (the slot join's per-node terminated segments, ascending
+// by slot, values read from the kind's state tables) is added by this rule
+// (include/kepler_accel.h; tests/tracker_ref.py restates it): a node keeps the
+// max_size best of (tracked ∪ batch) by target-zone energy; among equal
+// energies tracked items come first (eviction needs a strictly higher energy,
+// :124), then the batch in list order.  Where no item is dropped at the energy
+// of the last one kept this is what every Go map order keeps.  With ties at
+// that boundary the retained target-zone ENERGIES are still Go's, the retained
+// IDs are the rule's own choice and can differ from the Go heap's, whose choice
+// depends on its layout: max_size 2, adds of 101 (5 µJ), 102 (5 µJ), 103 (9 µJ)
+// — Go pops its root, the older 101, and keeps {102, 103}; the rule keeps
+// {101, 103}.  Each node's set is kept sorted (energy desc, then insertion
+// order), so one add is, per node (one wavefront each):
 //   filter  threshold, "beats the current minimum" when full, not tracked —
-//           in chunks of 64 candidates in slot order (equivalent, since the
-//           batch order breaks ties by slot)
+//           in chunks of 64 candidates in list order.  The chunks do not show:
+//           a chunk's survivors are tracked before the next chunk's, which is
+//           the list order at ties.  (`<=` against the minimum only saves work:
+//           a candidate AT the minimum would rank behind every tracked item
+//           and be cut.)  The one exception is the already-tracked check,
+//           made against the set as the candidate's chunk finds it: a key
+//           listed again after an earlier chunk of the same add evicted its
+//           tracked copy is a candidate again (in Go that case depends on the
+//           map order)
 //   sort    survivors by (energy desc, slot) — bitonic across the lanes
 //   merge   ranks by binary search (tracked i -> i + #survivors strictly
 //           above; survivor j -> j + #tracked at or above), then in place:
