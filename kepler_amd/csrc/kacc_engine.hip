@@ -37,10 +37,10 @@
 #include "kacc_derive.hpp"
 #include "kacc_device.hpp"
 #include "kacc_internal.hpp"
+#include "kacc_node.hpp"
 
 namespace kacc {
 
-constexpr int kTree = 256;                   // lanes of the canonical node-total tree
 constexpr int kRowsLds = 2048;               // Δcpu rows staged in LDS per node (16 KiB)
 constexpr int kBlock = 256;                  // namespace kernel workgroup
 template <int Z>
@@ -147,22 +147,8 @@ constexpr int kTpb = 512;  // threads per workgroup (fast path)
 template <int V>
 constexpr int kRpt = kRowsLds / kTpb<V>;            // fast-path rows per lane
 
-// device error bits (KACC_ERANGE)
-constexpr uint32_t kErrNode = 1u << 0;
-constexpr uint32_t kErrOffsets = 1u << 1;
-constexpr uint32_t kErrSlot = 1u << 2;
-constexpr uint32_t kErrNs = 1u << 3;
-constexpr uint32_t kErrCapacity = 1u << 4;
-constexpr uint32_t kErrBigNode = 1u << 5;  // oversized node under KACC_F_FAST_NODES
 static_assert(kRowsLds == KACC_FAST_MAX_PROCS && kTpb<0> == KACC_FAST_MAX_AGGREGATES,
               "KACC_FAST_* must match the fast path's capacity");
-
-// One big-node chunk (see big_node_prepare).  ctr_begin / vm_begin / pod_begin:
-// the first container / VM / pod the chunk owns; it owns them up to the next
-// chunk's begin (or the node's end for the last chunk).
-struct ChunkItem {
-  uint32_t node, chunk, nchunks, ctr_begin, vm_begin, pod_begin, pad[2];
-};
 
 // Cluster node totals (kacc_allreduce_namespaces, kacc_cluster_partials): one
 // block per output value — block c sums column c (node table c / Z of the five,
@@ -201,401 +187,6 @@ struct NodeTotalsArgs {
   uint32_t *arrived;            // [5Z] arrival counts, 0 between launches
 };
 
-struct DevState {
-  uint64_t *node_energy_total, *node_active_energy, *node_active_total, *node_idle_total;
-  double *node_power, *node_active_power, *node_idle_power;
-  int64_t *node_ts;
-  uint32_t *node_has_prev;
-  double *node_usage_ratio, *node_cpu_delta;
-  uint32_t *node_status;
-  uint64_t *proc_energy;
-  double *proc_ratio;   // [Sp] cpuTimeRatio of the slot's last attribution (power is derived)
-  uint32_t *proc_node;  // [Sp] the node that attribution belonged to
-  uint64_t *ctr_energy;
-  double *ctr_ratio, *ctr_cpu_delta, *ctr_cpu_total;  // container / VM power is derived (as processes')
-  uint32_t *ctr_node;
-  uint64_t *vm_energy;
-  double *vm_ratio, *vm_cpu_delta;
-  uint32_t *vm_node;
-  uint64_t *pod_energy;
-  double *pod_power, *pod_cpu_delta, *pod_cpu_total;
-  uint64_t proc_slots, ctr_slots, vm_slots, pod_slots;
-  uint32_t *err;
-  uint2 *defer;        // [defer_cap] (node, pod) pods left to pod_kernel
-  uint32_t *defer_ctr;  // [0] length; re-armed by interval_kernel
-  uint32_t defer_cap;
-  ChunkItem *items;    // [item_cap] big-node chunks this launch
-  uint32_t *item_ctr;  // [0] length, [1] dequeue head; cleared by pod_kernel
-  uint32_t item_cap;
-  // kacc_run_intervals over intervals of ONE layout (the same offset arrays):
-  // the chunk items are generated once (items_kernel) and reused, so the node
-  // phase skips them; pod_kernel keeps the list for the next interval
-  uint32_t items_given, keep_items;
-  uint64_t *stamps;  // kVarStamps only
-};
-
-struct NodeShared {
-  uint64_t active_energy[KACC_MAX_ZONES];
-  double power[KACC_MAX_ZONES];
-  double active_power[KACC_MAX_ZONES];
-  double node_delta;
-  uint32_t first;
-};
-
-__device__ __forceinline__ void raise_err(uint32_t *err, uint32_t bit) { atomicOr(err, bit); }
-
-// Block-uniform values live in SGPRs (saves VGPRs for rows in flight).
-__device__ __forceinline__ uint64_t uniform_u64(uint64_t x) {
-  const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x));
-  const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x >> 32));
-  return (static_cast<uint64_t>(hi) << 32) | lo;
-}
-__device__ __forceinline__ double uniform_f64(double x) {
-  return __longlong_as_double(static_cast<long long>(uniform_u64(static_cast<uint64_t>(__double_as_longlong(x)))));
-}
-__device__ __forceinline__ uint32_t uniform_u32(uint32_t x) { return __builtin_amdgcn_readfirstlane(x); }
-// a table pointer held in SGPRs, still known to be global memory (a pointer rebuilt from
-// an integer is generic: flat loads, which count on lgkmcnt too)
-template <typename T>
-__device__ __forceinline__ const T __attribute__((address_space(1))) *uniform_ptr(const T *p) {
-  return (const T __attribute__((address_space(1))) *)uniform_u64(reinterpret_cast<uint64_t>(p));
-}
-
-// Experiments (timing A/B only; results are identical): KACC_WT_PROC writes the
-// non-temporal row stores through the L2 (sc0 sc1 nt: no dirty line is left for
-// the end-of-kernel write-back), KACC_WT_AGG the aggregate rows likewise.
-// Experiment: extra dynamic LDS per interval_kernel workgroup (fewer resident
-// workgroups per CU, each with a larger share of the bandwidth: shorter lifetimes)
-#ifndef KACC_FAST_EXTRA_LDS
-#define KACC_FAST_EXTRA_LDS 0
-#endif
-#ifndef KACC_WT_PROC
-#define KACC_WT_PROC 0
-#endif
-#ifndef KACC_WT_AGG
-#define KACC_WT_AGG 0
-#endif
-template <typename T>
-__device__ __forceinline__ void wt_store(T v, T *p) {
-  if constexpr (sizeof(T) == 16)
-    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1 nt" ::"v"(p), "v"(v) : "memory");
-  else if constexpr (sizeof(T) == 8)
-    asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1 nt" ::"v"(p), "v"(v) : "memory");
-  else
-    asm volatile("global_store_dword %0, %1, off sc0 sc1 nt" ::"v"(p), "v"(v) : "memory");
-}
-template <typename T>
-__device__ __forceinline__ void nt_store(T v, T *p) {
-  if constexpr (KACC_WT_PROC != 0)
-    wt_store(v, p);
-  else
-    __builtin_nontemporal_store(v, p);
-}
-
-template <int Z>
-__device__ __forceinline__ void load_row(const uint64_t *__restrict__ base, uint64_t s,
-                                         uint64_t (&out)[Z]) {
-  if constexpr (Z % 2 == 0) {
-    using u64x2 = __attribute__((ext_vector_type(2))) unsigned long long;
-    const u64x2 *p = reinterpret_cast<const u64x2 *>(base + s * Z);
-#pragma unroll
-    for (int k = 0; k < Z / 2; ++k) {
-      const u64x2 x = p[k];
-      out[2 * k] = x.x;
-      out[2 * k + 1] = x.y;
-    }
-  } else {
-#pragma unroll
-    for (int z = 0; z < Z; ++z) out[z] = base[s * Z + z];
-  }
-}
-
-template <int Z>
-__device__ __forceinline__ void load_row_f64(const double *__restrict__ base, uint64_t s,
-                                             double (&out)[Z]) {
-  if constexpr (Z % 2 == 0) {
-    using f64x2 = __attribute__((ext_vector_type(2))) double;
-    const f64x2 *p = reinterpret_cast<const f64x2 *>(base + s * Z);
-#pragma unroll
-    for (int k = 0; k < Z / 2; ++k) {
-      const f64x2 x = p[k];
-      out[2 * k] = x.x;
-      out[2 * k + 1] = x.y;
-    }
-  } else {
-#pragma unroll
-    for (int z = 0; z < Z; ++z) out[z] = base[s * Z + z];
-  }
-}
-
-template <int Z, bool NT, typename T>
-__device__ __forceinline__ void store_row(T *__restrict__ base, uint64_t s, const T (&in)[Z]) {
-  if constexpr (Z % 2 == 0) {
-    using v2 = __attribute__((ext_vector_type(2))) T;
-    v2 *p = reinterpret_cast<v2 *>(base + s * Z);
-#pragma unroll
-    for (int k = 0; k < Z / 2; ++k) {
-      v2 x;
-      x.x = in[2 * k];
-      x.y = in[2 * k + 1];
-      if constexpr (NT)
-        nt_store(x, p + k);
-      else
-        p[k] = x;
-    }
-  } else {
-#pragma unroll
-    for (int z = 0; z < Z; ++z) {
-      if constexpr (NT)
-        nt_store(in[z], base + s * Z + z);
-      else
-        base[s * Z + z] = in[z];
-    }
-  }
-}
-
-// Pod rows are stored as one record per slot: the Z energy words then the Z
-// power words (KACC_T_POD_POWER's base is KACC_T_POD_ENERGY's + Z words), so a
-// pod's row is ONE 64-B gather at Z = 4 for the namespace totals (two 32-B rows
-// of two tables before: cluster partials 31.5 -> 22.0 us at config 3,
-// profiles/r03/abns).  load_row / store_row address base + s*Z, so a pod slot s
-// is passed as row 2s.
-constexpr uint64_t kPodRowScale = 2;
-__device__ __forceinline__ uint64_t pod_row(uint64_t s) { return s * kPodRowScale; }
-// the row index of aggregate slot s in its role's tables (1 container, 2 VM, 3 pod)
-__device__ __forceinline__ uint64_t agg_row(uint32_t role, uint64_t s) { return role == 3 ? pod_row(s) : s; }
-
-// Node-uniform attribution parameters (SGPRs) for the row passes.
-template <int Z>
-struct Attr {
-  uint64_t aE[Z];  // NodeUsage.activeEnergy
-  double aP[Z];    // NodeUsage.ActivePower
-  uint32_t live;   // bit z: zone passes the guard (ActivePower, activeEnergy, ΔcpuNode)
-  uint32_t live_pod;  // pod.go:96 guards on Power instead of ActivePower
-  double nd;       // ProcessTotalCPUTimeDelta
-  uint32_t first;  // first*Read variant: EnergyTotal = interval energy, Power 0
-  // KACC_F_STABLE_SLOT_NODES on a node past its first read: a row's slot already
-  // holds this node in KACC_T_PROC_NODE unless the row is NEW, so only NEW rows
-  // store it (4 B per process row less HBM traffic)
-  uint32_t keep_node;
-};
-
-// Attr from the node phase's LDS results (block-uniform -> SGPRs).
-template <int Z>
-__device__ __forceinline__ Attr<Z> make_attr(const NodeShared &sh, uint32_t flags) {
-  Attr<Z> a;
-  a.nd = uniform_f64(sh.node_delta);
-  a.first = uniform_u32(sh.first);
-  a.keep_node = (flags & KACC_F_STABLE_SLOT_NODES) && !a.first ? 1u : 0u;
-  a.live = 0;
-  a.live_pod = 0;
-#pragma unroll
-  for (int z = 0; z < Z; ++z) {
-    a.aE[z] = uniform_u64(sh.active_energy[z]);
-    a.aP[z] = uniform_f64(sh.active_power[z]);
-    const double pw = uniform_f64(sh.power[z]);
-    const bool ok = a.aE[z] != 0 && a.nd != 0;
-    if (ok && a.aP[z] != 0) a.live |= 1u << z;                       // process.go:124
-    if (ok && (a.first ? a.aP[z] : pw) != 0) a.live_pod |= 1u << z;  // pod.go:96 / :23
-  }
-  return a;
-}
-
-// process.go:118-148 (and its container/VM/pod twins) for one row.
-template <int Z>
-__device__ __forceinline__ double attribute_row(const Attr<Z> &a, uint32_t live, double delta,
-                                                bool is_new, const uint64_t (&prev)[Z],
-                                                uint64_t (&E)[Z], double (&P)[Z]) {
-  const double ratio = delta / a.nd;  // one IEEE division per row, never a reciprocal
-#pragma unroll
-  for (int z = 0; z < Z; ++z) {
-    if (live & (1u << z)) {
-      const uint64_t e = go_f64_to_u64(ratio * u2f(a.aE[z]));
-      E[z] = a.first ? e : e + (is_new ? 0ull : prev[z]);
-      P[z] = a.first ? 0.0 : ratio * a.aP[z];
-    } else {  // skipped zone keeps the zero Usage of newProcess (process.go:58-63)
-      E[z] = 0;
-      P[z] = 0.0;
-    }
-  }
-  return ratio;
-}
-
-// process.go:118-148 for one process row: the energy totals, and the row's
-// cpuTimeRatio (returned), which the state keeps INSTEAD of the Z powers: a
-// process's Power is ratio · the node's ActivePower when the zone passes the
-// guard (process.go:124, 142) — a function of the node's own tables of the same
-// interval (kacc_derive.hpp), derived wherever it is read.  8 + 4 bytes per row
-// (ratio, node) instead of 8Z.
-template <int Z>
-__device__ __forceinline__ double attribute_proc(const Attr<Z> &a, double delta, bool is_new,
-                                                 const uint64_t (&prev)[Z], uint64_t (&E)[Z]) {
-  const double ratio = delta / a.nd;  // one IEEE division per row, never a reciprocal
-#pragma unroll
-  for (int z = 0; z < Z; ++z) {
-    if (a.live & (1u << z)) {
-      const uint64_t e = go_f64_to_u64(ratio * u2f(a.aE[z]));
-      E[z] = a.first ? e : e + (is_new ? 0ull : prev[z]);
-    } else {  // skipped zone keeps the zero Usage of newProcess (process.go:58-63)
-      E[z] = 0;
-    }
-  }
-  return ratio;
-}
-
-// A process row's outputs at slot s: energy totals, ratio and node.
-template <int Z, bool NT>
-__device__ __forceinline__ void store_proc(const DevState &st, uint64_t s, const uint64_t (&E)[Z], double ratio,
-                                           uint32_t node, bool wnode) {
-  store_row<Z, NT, uint64_t>(st.proc_energy, s, E);
-  if constexpr (NT) {
-    nt_store(ratio, st.proc_ratio + s);
-    if (wnode) nt_store(node, st.proc_node + s);
-  } else {
-    st.proc_ratio[s] = ratio;
-    if (wnode) st.proc_node[s] = node;
-  }
-}
-
-// Cluster-total exports (kacc_interval.pod_export / node_export): what a pod /
-// node contributes to the cluster totals, in batch order, written by the
-// interval's own kernels so that kacc_allreduce_exports reduces them on
-// another stream while the next interval runs.  Pod row q: EnergyTotal[Z] then
-// the bits of Power[Z] (zeros for a pod whose slot is out of range).
-// Plain stores: a lane's record leaves as Z/2 + Z/2 16-B pieces, so each wave
-// instruction writes every 2Z-th 16 B of the wave's span; L2 merges the pieces
-// into full lines (non-temporal, each piece would reach HBM as a partial line).
-// The export row of batch pod q (kacc_interval.pod_export_pos: namespace order),
-// or ~0u when it is out of range (raised; nothing is written).
-__device__ __forceinline__ uint32_t export_row(const kacc_interval &b, uint32_t q, uint32_t *err) {
-  if (!b.pod_export_pos) return q;
-  const uint32_t r = b.pod_export_pos[q];
-  if (r >= b.n_pods) {
-    atomicOr(err, 1u << 1);  // kErrOffsets
-    return ~0u;
-  }
-  return r;
-}
-template <int Z>
-__device__ __forceinline__ void export_pod_at(const kacc_interval &b, uint32_t row, const uint64_t (&E)[Z],
-                                              const double (&P)[Z]) {
-  if (!b.pod_export || row == ~0u) return;
-  uint64_t *o = b.pod_export + static_cast<uint64_t>(row) * (2 * Z);
-  store_row<Z, false, uint64_t>(o, 0, E);
-  store_row<Z, false, double>(reinterpret_cast<double *>(o), 1, P);
-}
-template <int Z>
-__device__ __forceinline__ void export_pod(const kacc_interval &b, uint32_t q, const uint64_t (&E)[Z],
-                                           const double (&P)[Z], uint32_t *err) {
-  if (!b.pod_export) return;
-  export_pod_at<Z>(b, export_row(b, q, err), E, P);
-}
-template <int Z>
-__device__ __forceinline__ void export_pod_zero(const kacc_interval &b, uint32_t q, uint32_t *err) {
-  uint64_t E[Z];
-  double P[Z];
-#pragma unroll
-  for (int z = 0; z < Z; ++z) {
-    E[z] = 0;
-    P[z] = 0.0;
-  }
-  export_pod<Z>(b, q, E, P, err);
-}
-// Node n, zone z: ActiveEnergyTotal, IdleEnergyTotal, Power, ActivePower, IdlePower.
-template <int Z>
-__device__ __forceinline__ void export_node_zone(const kacc_interval &b, uint32_t n, uint32_t z, uint64_t at,
-                                                 uint64_t it, double p, double ap, double ip) {
-  if (!b.node_export) return;
-  uint64_t *o = b.node_export + static_cast<uint64_t>(n) * (5 * Z) + z;
-  o[0] = at;
-  o[Z] = it;
-  o[2 * Z] = static_cast<uint64_t>(__double_as_longlong(p));
-  o[3 * Z] = static_cast<uint64_t>(__double_as_longlong(ap));
-  o[4 * Z] = static_cast<uint64_t>(__double_as_longlong(ip));
-}
-
-// An aggregate row's outputs at slot s: energy totals; for a pod its powers,
-// for a container / VM its ratio and node (their power is derived on read as
-// a process's: the same guard, container.go:106-140, vm.go:78-109).
-template <int Z, typename T>
-__device__ __forceinline__ void wt_row(T *__restrict__ base, uint64_t s, const T (&in)[Z]) {
-  if constexpr (Z % 2 == 0) {
-    using v2 = __attribute__((ext_vector_type(2))) T;
-    v2 *p = reinterpret_cast<v2 *>(base + s * Z);
-#pragma unroll
-    for (int k = 0; k < Z / 2; ++k) {
-      v2 x;
-      x.x = in[2 * k];
-      x.y = in[2 * k + 1];
-      wt_store(x, p + k);
-    }
-  } else {
-#pragma unroll
-    for (int z = 0; z < Z; ++z) wt_store(in[z], base + s * Z + z);
-  }
-}
-
-template <int Z, bool NT>
-__device__ __forceinline__ void store_agg(const DevState &st, uint32_t role, uint64_t s, const uint64_t (&E)[Z],
-                                          const double (&P)[Z], double ratio, uint32_t node) {
-  if constexpr (KACC_WT_AGG != 0 && !NT) {
-    if (role == 3) {
-      wt_row<Z, uint64_t>(st.pod_energy, pod_row(s), E);
-      wt_row<Z, double>(st.pod_power, pod_row(s), P);
-      return;
-    }
-    wt_row<Z, uint64_t>(role == 1 ? st.ctr_energy : st.vm_energy, s, E);
-    wt_store(ratio, (role == 1 ? st.ctr_ratio : st.vm_ratio) + s);
-    wt_store(node, (role == 1 ? st.ctr_node : st.vm_node) + s);
-    return;
-  }
-  if (role == 3) {
-    store_row<Z, NT, uint64_t>(st.pod_energy, pod_row(s), E);
-    store_row<Z, NT, double>(st.pod_power, pod_row(s), P);
-    return;
-  }
-  store_row<Z, NT, uint64_t>(role == 1 ? st.ctr_energy : st.vm_energy, s, E);
-  double *r = role == 1 ? st.ctr_ratio : st.vm_ratio;
-  uint32_t *nd = role == 1 ? st.ctr_node : st.vm_node;
-  if constexpr (NT) {
-    nt_store(ratio, r + s);
-    nt_store(node, nd + s);
-  } else {
-    r[s] = ratio;
-    nd[s] = node;
-  }
-}
-
-// A container's CPU time (informer.go:229-233, 481-486): delta and total summed
-// over rows [i, e) of s_d in listing order — Go's order, so one lane adds them
-// one after the other.  kB reads are issued together per step; a tail step adds
-// +0.0 for rows past e, an identity on sums that start at +0.0 (neither sum can
-// ever be -0.0), and reads a clamped in-bounds row.
-template <int kB>
-__device__ __forceinline__ void segment_load(const double *s_d, uint32_t i, uint32_t e, double (&v)[kB]) {
-#pragma unroll
-  for (int u = 0; u < kB; ++u) v[u] = s_d[min(i + u, e - 1)];  // e > i: in bounds
-}
-template <int kB>
-__device__ __forceinline__ void segment_add(const double (&v)[kB], uint32_t i, uint32_t e, double &delta,
-                                            double &total) {
-#pragma unroll
-  for (int u = 0; u < kB; ++u) {
-    const double x = i + u < e ? v[u] : 0.0;
-    delta = delta + x;
-    total = total + x;
-  }
-}
-// One batch at a time (kernels short of registers).
-template <int kB>
-__device__ __forceinline__ void segment_sum(const double *s_d, uint32_t i, uint32_t e, double &delta,
-                                            double &total) {
-  for (; i < e; i += kB) {
-    double v[kB];
-    segment_load<kB>(s_d, i, e, v);
-    segment_add<kB>(v, i, e, delta, total);
-  }
-}
 // Slot sweep: a node whose rows' slots span at most kRowsLds slots (the slot
 // join keeps each node in its own slot range) is attributed in SLOT order:
 // 64-slot groups [smin + pos0, +64) moved with 1 KiB-contiguous wave
@@ -731,10 +322,6 @@ __device__ __forceinline__ void node_zone(const kacc_interval &b, const DevState
   if (z == 0) sh.first = first ? 1u : 0u;
 }
 
-struct NodeRanges {
-  uint32_t p0, p1, c0, c1, v0, v1, q0, q1;
-};
-
 // A skipped node (read error) keeps its snapshot (node.go:39-44): its exports
 // are its unchanged table values, lanes [lane, +nlanes) of the node's workers.
 template <int Z>
@@ -761,52 +348,6 @@ __device__ __forceinline__ void export_skipped(const kacc_interval &b, const Dev
       export_pod<Z>(b, q, E, P, st.err);
     }
   }
-}
-
-// Row ranges of node n, clamped so a malformed batch cannot fault.
-__device__ __forceinline__ NodeRanges clamp_ranges(const kacc_interval &b, const DevState &st, NodeRanges r,
-                                                   int tid);
-__device__ __forceinline__ NodeRanges node_ranges(const kacc_interval &b, const DevState &st,
-                                                  uint32_t n, int tid) {
-  return clamp_ranges(b, st,
-                      NodeRanges{b.proc_off[n], b.proc_off[n + 1], b.ctr_off[n], b.ctr_off[n + 1], b.vm_off[n],
-                                 b.vm_off[n + 1], b.pod_off[n], b.pod_off[n + 1]},
-                      tid);
-}
-
-// Status and row ranges of node n as ONE batch of vector loads through an index
-// the compiler must treat as per-lane, waited for once, then made uniform: as
-// scalar loads they took two dependent round trips (the offsets behind the
-// status branch) before a workgroup could issue its row loads.
-__device__ __forceinline__ void node_words(const kacc_interval &b, uint32_t n, uint32_t &status, NodeRanges &r) {
-  uint32_t ni = n;
-  asm volatile("" : "+v"(ni));
-  const uint32_t *sp = b.node_status ? b.node_status : b.proc_off;  // a stand-in address: no branch
-  const uint32_t s = sp[ni];
-  uint32_t w[8] = {b.proc_off[ni], b.proc_off[ni + 1], b.ctr_off[ni], b.ctr_off[ni + 1],
-                   b.vm_off[ni],   b.vm_off[ni + 1],   b.pod_off[ni], b.pod_off[ni + 1]};
-  asm volatile("" ::"v"(s), "v"(w[0]), "v"(w[1]), "v"(w[2]), "v"(w[3]), "v"(w[4]), "v"(w[5]), "v"(w[6]),
-               "v"(w[7]));  // the one wait
-  status = b.node_status ? __builtin_amdgcn_readfirstlane(s) : 0u;
-  auto u = [](uint32_t x) { return static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(x)); };
-  r = NodeRanges{u(w[0]), u(w[1]), u(w[2]), u(w[3]), u(w[4]), u(w[5]), u(w[6]), u(w[7])};
-}
-
-__device__ __forceinline__ NodeRanges clamp_ranges(const kacc_interval &b, const DevState &st, NodeRanges r,
-                                                   int tid) {
-  if (r.p1 > b.n_procs || r.p0 > r.p1 || r.c1 > b.n_ctrs || r.c0 > r.c1 || r.v1 > b.n_vms ||
-      r.v0 > r.v1 || r.q1 > b.n_pods || r.q0 > r.q1) {
-    if (tid == 0) raise_err(st.err, kErrOffsets);
-    r.p1 = min(r.p1, b.n_procs);
-    r.p0 = min(r.p0, r.p1);
-    r.c1 = min(r.c1, b.n_ctrs);
-    r.c0 = min(r.c0, r.c1);
-    r.v1 = min(r.v1, b.n_vms);
-    r.v0 = min(r.v0, r.v1);
-    r.q1 = min(r.q1, b.n_pods);
-    r.q0 = min(r.q0, r.q1);
-  }
-  return r;
 }
 
 template <int Z, int V>
@@ -1109,29 +650,12 @@ __device__ __forceinline__ void interval_node(const kacc_interval &b, const DevS
   const uint32_t utid = static_cast<uint32_t>(tid);
   auto role_of = [&]() -> uint32_t {
     if ((V & kVarSkipAggregates) != 0) return 0u;
-    return utid < nc ? 1u : utid < nc + nv ? 2u : utid < nc + nv + nq ? 3u : 0u;
+    return agg_role(utid, nc, nv, nq);
   };
-  auto index_of = [&]() -> uint32_t {  // position inside the role's range
-    return utid < nc ? utid : utid < nc + nv ? utid - nc : utid - nc - nv;
-  };
+  auto index_of = [&]() -> uint32_t { return agg_index(utid, nc, nv); };
   uint32_t a_beg = 0, a_end = 0, a_w = 0xffffffffu;
-  {
-    const uint32_t role = role_of(), j = index_of();
-    if (role == 1) {
-      a_beg = j == 0 ? p0 : b.ctr_proc_end[c0 + j - 1];
-      a_end = b.ctr_proc_end[c0 + j];
-      a_w = b.ctr_slot[c0 + j];
-    } else if (role == 2) {
-      a_beg = j == 0 ? (nc ? b.ctr_proc_end[c1 - 1] : p0) : b.vm_proc_end[v0 + j - 1];
-      a_end = b.vm_proc_end[v0 + j];
-      a_w = b.vm_slot[v0 + j];
-    } else if (role == 3) {
-      a_beg = j == 0 ? c0 : b.pod_ctr_end[q0 + j - 1];
-      a_end = b.pod_ctr_end[q0 + j];
-      a_w = b.pod_slot[q0 + j];
-    }
-  }
-  // the capacities as scalar values (capacities fit 31 bits, kacc_create): selected per lane
+  agg_segment(b, rg, role_of(), index_of(), a_beg, a_end, a_w);
+  // agg_cap with the capacities as scalar values (capacities fit 31 bits, kacc_create): selected per lane
   // from the kernel arguments they became a vector load, waited for with every load before it
   const uint32_t cap_c = uniform_u32(static_cast<uint32_t>(st.ctr_slots));
   const uint32_t cap_v = uniform_u32(static_cast<uint32_t>(st.vm_slots));
@@ -1145,12 +669,8 @@ __device__ __forceinline__ void interval_node(const kacc_interval &b, const DevS
   const bool a_ok = a_ok_f();
   const uint32_t role = role_of();
   const uint32_t j = index_of();
-  // per-role tables, re-derived at each use (keeps 8 VGPRs of pointers dead)
-  auto a_energy = [&]() { return role == 1 ? st.ctr_energy : role == 2 ? st.vm_energy : st.pod_energy; };
-  auto a_cpu_total = [&]() { return role == 1 ? st.ctr_cpu_total : st.pod_cpu_total; };
-  auto a_cpu_delta = [&]() {
-    return role == 1 ? st.ctr_cpu_delta : role == 2 ? st.vm_cpu_delta : st.pod_cpu_delta;
-  };
+  // the per-role tables (agg_energy, store_agg_cpu) are re-derived at each use (keeps 8 VGPRs
+  // of pointers dead)
   // Δ and the slot words go to LDS as they land (read after the first barrier):
   // the Δ registers are free before the dependent loads below are issued
 #pragma unroll
@@ -1176,16 +696,10 @@ __device__ __forceinline__ void interval_node(const kacc_interval &b, const DevS
   uint32_t smin = 0, span = 0;
   bool sweep = false;
   if constexpr (kSweepable || kRowSweep) {
-    if (b.node_proc_span) {
-      const uint32_t lo = uniform_u32(b.node_proc_span[2 * n]);
-      const uint32_t hi = uniform_u32(b.node_proc_span[2 * n + 1]);
-      sweep = rows > 0 && hi >= lo && hi - lo < static_cast<uint32_t>(kRowsLds) && hi < st.proc_slots;
-      smin = lo;
-      span = hi - lo + 1;
-      if (sweep) {
+    sweep = sweep_span(b, st, n, rows, static_cast<uint32_t>(kRowsLds), smin, span);
+    if (sweep) {
 #pragma unroll
-        for (int k = 0; k < kRowsPerThread; ++k) s_inv[tid + k * kThreads] = 0xffffu;
-      }
+      for (int k = 0; k < kRowsPerThread; ++k) s_inv[tid + k * kThreads] = 0xffffu;
     }
   }
   const bool swept = (kSweepable || kRowSweep) && sweep;
@@ -1210,26 +724,21 @@ __device__ __forceinline__ void interval_node(const kacc_interval &b, const DevS
       for (int k = 0; k < kRowsPerThread; ++k) {
         const uint64_t sl = w[k] & KACC_SLOT_MASK;
         if constexpr (kTransposed<Z> && (V & kVarNoTranspose) == 0) {
-          const uint64_t g0 = uniform_u32(static_cast<uint32_t>(sl));  // lane 0's slot
-          if (__all((tid + k * kThreads) < rows && sl == g0 + (tid & 63) && g0 + 64 <= st.proc_slots)) {
+          uint64_t g0;
+          if (group_is_contiguous(st, (tid + k * kThreads) < rows, sl, g0)) {
             contig |= 1u << k;
             load_group_masked<Z, false, kNtLd>(st.proc_energy, g0, 64u, g0, prev[k]);
             continue;
           }
         }
-        if (sl < st.proc_slots) {
-          load_row<Z>(st.proc_energy, sl, prev[k]);
-        } else {
-#pragma unroll
-          for (int z = 0; z < Z; ++z) prev[k][z] = 0;
-        }
+        load_prev_or_zero<Z>(st, true, sl, prev[k]);  // no row: its slot word is past every table
       }
     }
   }
   uint64_t a_prev[Z];
   double a_total = 0.0;
   if (a_ok) {
-    if constexpr (!kLateAgg<V>) load_row<Z>(a_energy(), agg_row(role, a_s), a_prev);
+    if constexpr (!kLateAgg<V>) load_row<Z>(agg_energy(st, role), agg_row(role, a_s), a_prev);
     // the tables as scalar pointers: selected per lane from the kernel arguments they
     // became a vector load of the pointer, waited for with every load before it (the
     // rows' previous totals among them) before the running total's load could issue
@@ -1252,12 +761,7 @@ __device__ __forceinline__ void interval_node(const kacc_interval &b, const DevS
 #pragma unroll
     for (int k = 0; k < kRowsPerThread; ++k) {
       const uint32_t r = tid + k * kThreads;
-      if (r >= rows) continue;
-      const uint32_t sl = s_w[r] & KACC_SLOT_MASK;
-      if (sl - smin < span && sl < st.proc_slots)
-        s_inv[sl - smin] = static_cast<uint16_t>(r);
-      else  // outside the node's span / the table: not attributed
-        raise_err(st.err, kErrSlot);
+      if (r < rows) fill_inverse(st, s_inv, s_w[r], smin, span, r);
     }
   }
   if (b.flags & KACC_F_NODE_CPU_DELTA_GIVEN) {
@@ -1274,57 +778,30 @@ __device__ __forceinline__ void interval_node(const kacc_interval &b, const DevS
       red[tid] = s;
     }
     __syncthreads();
-    if (tid < 128) red[tid] = red[tid] + red[tid + 128];
-    __syncthreads();
-    if (tid < 64) {
-      double x = red[tid] + red[tid + 64];
-#pragma unroll
-      for (int k = 32; k >= 1; k >>= 1) x = x + __shfl_down(x, k, 64);
-      if (tid == 0) sh.node_delta = x;
-    }
+    const double x = block_tree_sum(red, tid);
+    if (tid == 0) sh.node_delta = x;
   }
 
   // ---- C: containers and VMs (segmented sums, one lane per segment) ----------
   double a_delta = 0.0;
   if (role == 1 || role == 2) {
     uint32_t beg = a_beg, end = a_end;
-    if (beg < p0 || end < beg || end > p1) {
-      raise_err(st.err, kErrOffsets);
-      beg = max(min(beg, p1), p0);
-      end = max(min(end, p1), beg);
-    }
+    clamp_segment(beg, end, p0, p1, st.err);
+    segment_cpu<8>(s_d, role, beg - p0, end - p0, a_delta, a_total);
     if (role == 1) {
-      // resetCPUTime on the first process (informer.go:229-233, 481-486)
-      segment_sum<8>(s_d, beg - p0, end - p0, a_delta, a_total);
       s_cd[j] = a_ok ? a_delta : 0.0;
       s_ct[j] = a_ok ? a_total : 0.0;
-    } else {
-      // updateVMCache (informer.go:445): the last process in listing order wins
-      a_delta = end > beg ? s_d[end - 1 - p0] : 0.0;
     }
-    if (a_ok) {
-      a_cpu_delta()[a_s] = a_delta;
-      if (role == 1) a_cpu_total()[a_s] = a_total;
-    }
+    if (a_ok) store_agg_cpu(st, role, a_s, a_delta, a_total);
   }
   __syncthreads();
 
-  // ---- D: pods (informer.go:305-309, 502-507) ----------------------------------
+  // ---- D: pods ---------------------------------------------------------------------
   if (role == 3) {
     uint32_t beg = a_beg, end = a_end;
-    if (beg < c0 || end < beg || end > c1) {
-      raise_err(st.err, kErrOffsets);
-      beg = max(min(beg, c1), c0);
-      end = max(min(end, c1), beg);
-    }
-    for (uint32_t c = beg - c0; c < end - c0; ++c) {
-      a_delta = a_delta + s_cd[c];
-      a_total = a_total + s_ct[c];  // quirk: the container's running total
-    }
-    if (a_ok) {
-      a_cpu_delta()[a_s] = a_delta;
-      a_cpu_total()[a_s] = a_total;
-    }
+    clamp_segment(beg, end, c0, c1, st.err);
+    pod_sum(s_cd, s_ct, beg - c0, end - c0, a_delta, a_total);
+    if (a_ok) store_agg_cpu(st, 3u, a_s, a_delta, a_total);
   }
 
   // ---- E: attribution ------------------------------------------------------------
@@ -1332,13 +809,7 @@ __device__ __forceinline__ void interval_node(const kacc_interval &b, const DevS
   if constexpr (kStamp) {
     if (tid == 0) stamp[2] = __builtin_amdgcn_s_memrealtime();
   }
-  if (tid == 0) {  // node scalars of the new snapshot
-    st.node_ts[n] = b.node_ts_ns[n];
-    st.node_has_prev[n] = 1u;
-    st.node_usage_ratio[n] = a.first ? 0.0 : b.node_usage_ratio[n];  // firstNodeRead leaves 0
-    st.node_cpu_delta[n] = a.nd;
-    st.node_status[n] = a.first ? KACC_NODE_FIRST_READ : KACC_NODE_OK;
-  }
+  if (tid == 0) store_node_scalars(st, n, a.first, a.nd, b.node_ts_ns[n], b.node_usage_ratio[n]);
   // A batch-order pod export (no pod_export_pos) leaves through LDS: the node's pods are
   // export rows [q0, q1), so after the process pass (s_d free) each pod lane puts its
   // record in s_d and the workgroup writes the node's records as one contiguous run of
@@ -1360,14 +831,12 @@ __device__ __forceinline__ void interval_node(const kacc_interval &b, const DevS
       }
       return;
     }
-    if constexpr (kLateAgg<V>) load_row<Z>(a_energy(), agg_row(role, a_s), a_prev);
+    if constexpr (kLateAgg<V>) load_row<Z>(agg_energy(st, role), agg_row(role, a_s), a_prev);
     // a pod's export row (namespace order) loads beside its previous totals: no extra round trip
     const uint32_t xrow = role == 3 && b.pod_export && !stage ? export_row(b, q0 + j, st.err) : ~0u;
     uint64_t E[Z];
     double P[Z];
-    const double ratio = attribute_row<Z>(a, role == 3 ? a.live_pod : a.live, a_delta,
-                                          (a_w & KACC_SLOT_NEW) != 0, a_prev, E, P);
-    store_agg<Z, kNtAgg>(st, role, a_s, E, P, ratio, n);
+    aggregate_row<Z, kNtAgg>(st, a, role, a_w, a_delta, a_prev, n, E, P);
     if (role == 3) {
       if (stage) {
 #pragma unroll
@@ -1775,6 +1244,8 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4, 4))) void 
     const double ratio = uniform_f64(tab.ratio[e]), nd_given = uniform_f64(tab.nd_given[e]);
     const uint32_t zl = tid < static_cast<uint32_t>(Z) ? tid : 0u;
     const uint64_t ze = tab.ze[e * Z + zl], zm = tab.zm[e * Z + zl];
+    // mirrors agg_role / agg_begin over the prefetched descriptors (load_rows read them at clamped
+    // indices): written out, so that the kernel's code stays the one its spills were tuned at
     const bool is_c = tid < nc, is_v = !is_c && tid < nc + nv, is_q = !is_c && !is_v && tid < nc + nv + nq;
     const uint32_t a_beg0 = is_c   ? (tid == 0 ? p0 : rw.cb)
                             : is_v ? (tid == nc ? (nc ? rw.cre : p0) : rw.vb)
@@ -1784,6 +1255,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4, 4))) void 
     const uint32_t a_w = is_c ? rw.cw : is_v ? rw.vw : is_q ? rw.qw : 0xffffffffu;
     // slot sweep this interval? (block-uniform)
     const uint32_t s_lo = uniform_u32(tab.span_lo[e]), s_hi = uniform_u32(tab.span_hi[e]);
+    // mirrors span_sweeps (kacc_node.hpp)
     const bool sweep = rows > 0 && s_hi >= s_lo && s_hi - s_lo < static_cast<uint32_t>(kRows) && s_hi < st.proc_slots;
     const uint32_t span = sweep ? s_hi - s_lo + 1 : 0u;
     if (sweep != (c_sbase != kNoWindow)) {  // layout change: drop the row keys / start an empty map
@@ -1805,7 +1277,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4, 4))) void 
           if (process && pos < span)
             s_inv[pos] = static_cast<uint16_t>(r);
           else
-            outside = process;  // a row outside its node's span: not computed
+            outside = process;  // fill_inverse's rule (a span that sweeps lies inside the table), reported once
         } else {
           moved |= (rw.w[j] & KACC_SLOT_MASK) != (s_cw[r] & KACC_SLOT_MASK);
         }
@@ -1831,6 +1303,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4, 4))) void 
       // ---- this lane's aggregate; did any position move? ---------------------------------
       const uint32_t role = (V & kCarryNoAggregates) ? 0u : is_c ? 1u : is_v ? 2u : is_q ? 3u : 0u;
       const uint32_t a_s = a_w & KACC_SLOT_MASK;
+      // mirrors agg_cap (kacc_node.hpp)
       const uint64_t a_cap = role == 1 ? st.ctr_slots : role == 2 ? st.vm_slots : role == 3 ? st.pod_slots : 0;
       const bool a_ok = role != 0 && a_s < a_cap;
       if (role != 0 && !a_ok) raise_err(st.err, kErrSlot);
@@ -1865,7 +1338,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4, 4))) void 
             const uint64_t sl = sw & KACC_SLOT_MASK;
             if (sl == (s_cw[r] & KACC_SLOT_MASK)) continue;
             uint64_t pv[Z];
-            if (sl < st.proc_slots) {
+            if (sl < st.proc_slots) {  // mirrors load_prev_or_zero (kacc_node.hpp)
               load_row<Z>(st.proc_energy, sl, pv);
             } else {
 #pragma unroll
@@ -1876,6 +1349,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4, 4))) void 
           }
         }
         if (a_moved) {
+          // mirrors agg_energy (kacc_node.hpp)
           load_row<Z>(role == 1 ? st.ctr_energy : role == 2 ? st.vm_energy : st.pod_energy, agg_row(role, a_s), c_aE);
           c_atotal = role == 1 ? st.ctr_cpu_total[a_s] : role == 3 ? st.pod_cpu_total[a_s] : 0.0;
         }
@@ -1914,15 +1388,13 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4, 4))) void 
         if (tid == 0) sh.first = first ? 1u : 0u;
       }
       // ---- B: ProcessTotalCPUTimeDelta (informer.go:330-333) by the last wave, while the
-      //      others sum containers: interval_kernel's canonical 256-leaf tree evaluated by
-      //      64 lanes as small_kernel does (lane t: leaves t, t+64, t+128, t+192, each the
-      //      in-order sum of rows l, l+256, ...) — the same additions in the same order
+      //      others sum containers: the canonical tree on 64 lanes (node_delta_tree64)
       if (flags & KACC_F_NODE_CPU_DELTA_GIVEN) {
         if (tid == 0) sh.node_delta = nd_given;
       } else if (tid >= static_cast<uint32_t>(kThreads - 64)) {
         const uint32_t t = tid - (kThreads - 64);
-        // a leaf's LDS reads issued together (r < kRows: in bounds); a row past the
-        // node's end adds +0.0, an identity on a sum that starts at +0.0
+        // mirrors node_delta_tree64 (kacc_node.hpp): a leaf's LDS reads issued together (r < kRows: in
+        // bounds); a row past the node's end adds +0.0, an identity on a sum that starts at +0.0
         constexpr int kU = kRows / kTree, kB = kU < 4 ? kU : 4;  // reads in flight
         double leaf[4];
 #pragma unroll
@@ -1950,12 +1422,8 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4, 4))) void 
       double a_delta = 0.0;
       if (role == 1 || role == 2) {
         uint32_t beg = a_beg0, end = a_end0;
-        if (beg < p0 || end < beg || end > p1) {
-          raise_err(st.err, kErrOffsets);
-          beg = max(min(beg, p1), p0);
-          end = max(min(end, p1), beg);
-        }
-        if (role == 1) {  // informer.go:229-233, 481-486: in order, 4 LDS reads in flight
+        clamp_segment(beg, end, p0, p1, st.err);
+        if (role == 1) {  // segment_cpu, with the container's LDS sums in its branch
           segment_sum<4>(s_d, beg - p0, end - p0, a_delta, a_total);
           s_cd[tid] = a_ok ? a_delta : 0.0;
           s_ct[tid] = a_ok ? a_total : 0.0;
@@ -1966,18 +1434,11 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4, 4))) void 
       mark(2);
       lds_barrier();
       mark(3);
-      // ---- D: pods (informer.go:305-309, 502-507) -----------------------------------------
+      // ---- D: pods ---------------------------------------------------------------------------
       if (role == 3) {
         uint32_t beg = a_beg0, end = a_end0;
-        if (beg < c0 || end < beg || end > c1) {
-          raise_err(st.err, kErrOffsets);
-          beg = max(min(beg, c1), c0);
-          end = max(min(end, c1), beg);
-        }
-        for (uint32_t c = beg - c0; c < end - c0; ++c) {
-          a_delta = a_delta + s_cd[c];
-          a_total = a_total + s_ct[c];  // quirk: the container's running total
-        }
+        clamp_segment(beg, end, c0, c1, st.err);
+        pod_sum(s_cd, s_ct, beg - c0, end - c0, a_delta, a_total);
       }
       // ---- E: attribution; the prefetch lands before the first store -----------------------
       if constexpr (kPrefetch) {
@@ -1994,15 +1455,15 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4, 4))) void 
         st.node_idle_power[zi] = z_ip;
       }
       const Attr<Z> a = make_attr<Z>(sh, b.flags);
-      if (tid == 0) {
+      if (tid == 0) {  // mirrors store_node_scalars (kacc_node.hpp)
         st.node_ts[n] = ts;
         st.node_has_prev[n] = 1u;
         st.node_usage_ratio[n] = a.first ? 0.0 : ratio;
         st.node_cpu_delta[n] = a.nd;
         st.node_status[n] = a.first ? KACC_NODE_FIRST_READ : KACC_NODE_OK;
       }
-      if (a_ok) {  // container.go:106-140 / vm.go:78-109 / pod.go:87-118
-        if (role == 1) {
+      if (a_ok) {
+        if (role == 1) {  // mirrors store_agg_cpu (kacc_node.hpp)
           st.ctr_cpu_delta[a_s] = a_delta;
           st.ctr_cpu_total[a_s] = a_total;
         } else if (role == 2) {
@@ -2013,9 +1474,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4, 4))) void 
         }
         uint64_t E[Z];
         double P[Z];
-        const double ratio =
-            attribute_row<Z>(a, role == 3 ? a.live_pod : a.live, a_delta, (a_w & KACC_SLOT_NEW) != 0, c_aE, E, P);
-        store_agg<Z, kNtAggStores || (V & kCarryNtAgg) != 0>(st, role, a_s, E, P, ratio, n);
+        aggregate_row<Z, kNtAggStores || (V & kCarryNtAgg) != 0>(st, a, role, a_w, a_delta, c_aE, n, E, P);
 #pragma unroll
         for (int z = 0; z < Z; ++z) c_aE[z] = E[z];
         c_atotal = a_total;
@@ -2191,16 +1650,10 @@ __global__ __launch_bounds__(64 * kSmallWaves) __attribute__((amdgpu_waves_per_e
   uint32_t smin = 0, span = 0;
   bool swept = false;
   if constexpr (kSweepable || kRowSweep) {
-    if (b.node_proc_span) {
-      const uint32_t lo = uniform_u32(b.node_proc_span[2 * n]);
-      const uint32_t hi = uniform_u32(b.node_proc_span[2 * n + 1]);
-      swept = rows > 0 && hi >= lo && hi - lo < static_cast<uint32_t>(kSmallRows) && hi < st.proc_slots;
-      smin = lo;
-      span = hi - lo + 1;
-      if (swept) {
+    swept = sweep_span(b, st, n, rows, static_cast<uint32_t>(kSmallRows), smin, span);
+    if (swept) {
 #pragma unroll
-        for (int k = 0; k < kSmallGroups; ++k) s_inv[lane + 64u * k] = 0xffffu;
-      }
+      for (int k = 0; k < kSmallGroups; ++k) s_inv[lane + 64u * k] = 0xffffu;
     }
   }
   // batch kb (groups 4kb .. 4kb+3): previous totals into prev; bit g of contig:
@@ -2231,69 +1684,33 @@ __global__ __launch_bounds__(64 * kSmallWaves) __attribute__((amdgpu_waves_per_e
       const uint32_t wk = (from_regs || !kSweepable) ? w[k] : (r < rows ? s_w[r] : 0xffffffffu);
       const uint64_t sl = wk & KACC_SLOT_MASK;
       if constexpr (kTransposed<Z>) {
-        const uint64_t g0 = uniform_u32(static_cast<uint32_t>(sl));
-        if (__all(r < rows && sl == g0 + lane && g0 + 64 <= st.proc_slots)) {
+        uint64_t g0;
+        if (group_is_contiguous(st, r < rows, sl, g0)) {
           contig |= 1u << g;
           load_group_masked<Z, false, kNtLd>(st.proc_energy, g0, 64u, g0, prev[g]);
           continue;
         }
       }
-      if (r < rows && sl < st.proc_slots) {
-        load_row<Z>(st.proc_energy, sl, prev[g]);
-      } else {
-#pragma unroll
-        for (int z = 0; z < Z; ++z) prev[g][z] = 0;
-      }
+      load_prev_or_zero<Z>(st, r < rows, sl, prev[g]);
     }
   };
   load_batch(0, true);
 
   // aggregates: lane handles aggregate i = lane + 64h (containers, VMs, pods)
-  auto role_of = [&](uint32_t i) -> uint32_t {
-    return i < nc ? 1u : i < nc + nv ? 2u : i < nc + nv + nq ? 3u : 0u;
-  };
-  auto index_of = [&](uint32_t i) -> uint32_t { return i < nc ? i : i < nc + nv ? i - nc : i - nc - nv; };
-  auto cap_of = [&](uint32_t role) -> uint64_t {
-    return role == 1 ? st.ctr_slots : role == 2 ? st.vm_slots : role == 3 ? st.pod_slots : 0;
-  };
-  auto energy_of = [&](uint32_t role) { return role == 1 ? st.ctr_energy : role == 2 ? st.vm_energy : st.pod_energy; };
-  auto cpu_total_of = [&](uint32_t role) { return role == 1 ? st.ctr_cpu_total : st.pod_cpu_total; };
-  auto cpu_delta_of = [&](uint32_t role) {
-    return role == 1 ? st.ctr_cpu_delta : role == 2 ? st.vm_cpu_delta : st.pod_cpu_delta;
-  };
+  auto role_of = [&](uint32_t i) -> uint32_t { return agg_role(i, nc, nv, nq); };
+  auto index_of = [&](uint32_t i) -> uint32_t { return agg_index(i, nc, nv); };
   uint32_t a_beg[2], a_end[2], a_w[2];
   uint64_t a_prev[2][Z];
   double a_total[2], a_delta[2];
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
-    const uint32_t i = lane + 64u * h, role = role_of(i), j = index_of(i);
+    const uint32_t i = lane + 64u * h, role = role_of(i);
     a_beg[h] = a_end[h] = 0;
     a_w[h] = 0xffffffffu;
-    if (role == 1) {
-      a_beg[h] = j == 0 ? p0 : b.ctr_proc_end[c0 + j - 1];
-      a_end[h] = b.ctr_proc_end[c0 + j];
-      a_w[h] = b.ctr_slot[c0 + j];
-    } else if (role == 2) {
-      a_beg[h] = j == 0 ? (nc ? b.ctr_proc_end[c1 - 1] : p0) : b.vm_proc_end[rg.v0 + j - 1];
-      a_end[h] = b.vm_proc_end[rg.v0 + j];
-      a_w[h] = b.vm_slot[rg.v0 + j];
-    } else if (role == 3) {
-      a_beg[h] = j == 0 ? c0 : b.pod_ctr_end[q0 + j - 1];
-      a_end[h] = b.pod_ctr_end[q0 + j];
-      a_w[h] = b.pod_slot[q0 + j];
-    }
-    const uint32_t a_s = a_w[h] & KACC_SLOT_MASK;
-    const bool a_ok = role != 0 && a_s < cap_of(role);
-    a_total[h] = 0.0;
+    agg_segment(b, rg, role, index_of(i), a_beg[h], a_end[h], a_w[h]);
     a_delta[h] = 0.0;
-    if (a_ok) {
-      load_row<Z>(energy_of(role), agg_row(role, a_s), a_prev[h]);
-      if (role != 2 && !(a_w[h] & KACC_SLOT_NEW)) a_total[h] = cpu_total_of(role)[a_s];
-    } else {
-#pragma unroll
-      for (int z = 0; z < Z; ++z) a_prev[h][z] = 0;
-    }
-    if (role != 0 && !a_ok) raise_err(st.err, kErrSlot);
+    load_agg_prev<Z>(st, role, a_w[h], role != 0 && (a_w[h] & KACC_SLOT_MASK) < agg_cap(st, role), a_prev[h],
+                     a_total[h]);
   }
 
   // ---- B: stage Δ / slot words; ProcessTotalCPUTimeDelta (informer.go:330-333) ------
@@ -2310,47 +1727,20 @@ __global__ __launch_bounds__(64 * kSmallWaves) __attribute__((amdgpu_waves_per_e
 #pragma unroll
     for (int k = 0; k < kSmallGroups; ++k) {
       const uint32_t r = lane + 64u * k;
-      if (r >= rows) continue;
-      const uint32_t sl = w[k] & KACC_SLOT_MASK;
-      if (sl - smin < span && sl < st.proc_slots)
-        s_inv[sl - smin] = static_cast<uint16_t>(r | ((w[k] & KACC_SLOT_NEW) ? 0x8000u : 0u));
-      else
-        raise_err(st.err, kErrSlot);
+      if (r < rows) fill_inverse(st, s_inv, w[k], smin, span, r | ((w[k] & KACC_SLOT_NEW) ? 0x8000u : 0u));
     }
   }
   if (kSweepable && swept) {
 #pragma unroll
     for (int k = 0; k < kSmallGroups; ++k) {
       const uint32_t r = lane + 64u * k;
-      if (r >= rows) continue;
-      const uint32_t sl = s_w[r] & KACC_SLOT_MASK;
-      if (sl - smin < span && sl < st.proc_slots)
-        s_inv[sl - smin] = static_cast<uint16_t>(r);
-      else
-        raise_err(st.err, kErrSlot);
+      if (r < rows) fill_inverse(st, s_inv, s_w[r], smin, span, r);
     }
   }
   if (b.flags & KACC_F_NODE_CPU_DELTA_GIVEN) {
     if (lane == 0) sh.node_delta = b.node_cpu_delta[n];
   } else {
-    // the 256 tree leaves of interval_kernel: leaf l sums rows l, l+256 in order;
-    // lane t holds leaves t, t+64, t+128, t+192; then red[l] + red[l+128],
-    // red[t] + red[t+64] and the shuffle tree, exactly as there
-    double leaf[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const uint32_t r0 = lane + 64u * q, r1 = r0 + kTree;  // both < kSmallRows: in bounds
-      const double v0 = s_d[r0], v1 = s_d[r1];
-      double s = 0.0;
-      s = s + (r0 < rows ? v0 : 0.0);  // +0.0 past the node's end: an identity
-      s = s + (r1 < rows ? v1 : 0.0);
-      leaf[q] = s;
-    }
-    const double t0 = leaf[0] + leaf[2];
-    const double t1 = leaf[1] + leaf[3];
-    double x = t0 + t1;
-#pragma unroll
-    for (int k = 32; k >= 1; k >>= 1) x = x + __shfl_down(x, k, 64);
+    const double x = node_delta_tree64<kSmallRows>(s_d, lane, rows);
     if (lane == 0) sh.node_delta = x;
   }
 
@@ -2360,86 +1750,51 @@ __global__ __launch_bounds__(64 * kSmallWaves) __attribute__((amdgpu_waves_per_e
     const uint32_t i = lane + 64u * h, role = role_of(i), j = index_of(i);
     if (role != 1 && role != 2) continue;
     const uint32_t a_s = a_w[h] & KACC_SLOT_MASK;
-    const bool a_ok = a_s < cap_of(role);
+    const bool a_ok = a_s < agg_cap(st, role);
     uint32_t beg = a_beg[h], end = a_end[h];
-    if (beg < p0 || end < beg || end > p1) {
-      raise_err(st.err, kErrOffsets);
-      beg = max(min(beg, p1), p0);
-      end = max(min(end, p1), beg);
-    }
-    double ad = 0.0;
-    if (role == 1) {  // informer.go:229-233, 481-486
-      double at = a_total[h];
-      segment_sum<4>(s_d, beg - p0, end - p0, ad, at);
+    clamp_segment(beg, end, p0, p1, st.err);
+    double ad = 0.0, at = a_total[h];
+    segment_cpu<4>(s_d, role, beg - p0, end - p0, ad, at);
+    if (role == 1) {
       a_total[h] = at;
       s_cd[j] = a_ok ? ad : 0.0;
       s_ct[j] = a_ok ? at : 0.0;
-    } else {  // informer.go:445: the last process in listing order wins
-      ad = end > beg ? s_d[end - 1 - p0] : 0.0;
     }
     a_delta[h] = ad;
-    if (a_ok) {
-      cpu_delta_of(role)[a_s] = ad;
-      if (role == 1) cpu_total_of(role)[a_s] = a_total[h];
-    }
+    if (a_ok) store_agg_cpu(st, role, a_s, ad, at);
   }
   wave_sync();
 
-  // ---- D: pods (informer.go:305-309, 502-507) ---------------------------------------
+  // ---- D: pods -------------------------------------------------------------------------
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     const uint32_t i = lane + 64u * h;
     if (role_of(i) != 3) continue;
     const uint32_t a_s = a_w[h] & KACC_SLOT_MASK;
     uint32_t beg = a_beg[h], end = a_end[h];
-    if (beg < c0 || end < beg || end > c1) {
-      raise_err(st.err, kErrOffsets);
-      beg = max(min(beg, c1), c0);
-      end = max(min(end, c1), beg);
-    }
+    clamp_segment(beg, end, c0, c1, st.err);
     double ad = 0.0, at = a_total[h];
-    for (uint32_t c = beg - c0; c < end - c0; ++c) {
-      ad = ad + s_cd[c];
-      at = at + s_ct[c];  // quirk: the container's running total
-    }
+    pod_sum(s_cd, s_ct, beg - c0, end - c0, ad, at);
     a_delta[h] = ad;
     a_total[h] = at;
-    if (a_s < st.pod_slots) {
-      st.pod_cpu_delta[a_s] = ad;
-      st.pod_cpu_total[a_s] = at;
-    }
+    if (a_s < st.pod_slots) store_agg_cpu(st, 3u, a_s, ad, at);
   }
 
   // ---- E: attribution ------------------------------------------------------------------
   const Attr<Z> a = make_attr<Z>(sh, KACC_SMALL_STABLE ? b.flags : (b.flags & ~KACC_F_STABLE_SLOT_NODES));
-  if (lane == 0) {
-    st.node_ts[n] = b.node_ts_ns[n];
-    st.node_has_prev[n] = 1u;
-    st.node_usage_ratio[n] = a.first ? 0.0 : b.node_usage_ratio[n];
-    st.node_cpu_delta[n] = a.nd;
-    st.node_status[n] = a.first ? KACC_NODE_FIRST_READ : KACC_NODE_OK;
-  }
+  if (lane == 0) store_node_scalars(st, n, a.first, a.nd, b.node_ts_ns[n], b.node_usage_ratio[n]);
   // aggregate rows: stored after the process rows when KACC_SMALL_LATE_AGG (as
   // interval_kernel's KACC_LATE_AGG: early rows sit dirty in L2 through the stream)
-  auto aggregate_out = [&]() {
+  auto aggregates_out = [&]() {
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {  // container.go:106-140 / vm.go:78-109 / pod.go:87-118
+    for (int h = 0; h < 2; ++h) {
       const uint32_t i = lane + 64u * h, role = role_of(i);
-      const uint32_t a_s = a_w[h] & KACC_SLOT_MASK;
       if (role == 0) continue;
-      if (a_s >= cap_of(role)) {
-        if (role == 3) export_pod_zero<Z>(b, q0 + index_of(i), st.err);
-        continue;
-      }
-      uint64_t E[Z];
-      double P[Z];
-      const double ratio = attribute_row<Z>(a, role == 3 ? a.live_pod : a.live, a_delta[h],
-                                            (a_w[h] & KACC_SLOT_NEW) != 0, a_prev[h], E, P);
-      store_agg<Z, kNT && kNtAggStores>(st, role, a_s, E, P, ratio, n);
-      if (role == 3) export_pod<Z>(b, q0 + index_of(i), E, P, st.err);
+      aggregate_out<Z, kNT && kNtAggStores>(b, st, a, role, a_w[h], (a_w[h] & KACC_SLOT_MASK) < agg_cap(st, role),
+                                            a_delta[h], a_prev[h], n, q0 + index_of(i));
     }
   };
-  if constexpr (KACC_SMALL_LATE_AGG == 0) aggregate_out();
+  if constexpr (KACC_SMALL_LATE_AGG == 0) aggregates_out();
   auto attr_batch = [&](int kb) {  // process.go:118-148
 #pragma unroll
     for (int g = 0; g < kSmallBatch; ++g) {
@@ -2493,7 +1848,7 @@ __global__ __launch_bounds__(64 * kSmallWaves) __attribute__((amdgpu_waves_per_e
     load_batch(1, false);
     attr_batch(1);
   }
-  if constexpr (KACC_SMALL_LATE_AGG != 0) aggregate_out();
+  if constexpr (KACC_SMALL_LATE_AGG != 0) aggregates_out();
 }
 
 // ======================= big nodes: chunked row passes ==========================
@@ -2670,24 +2025,11 @@ __device__ void big_node_prepare(const kacc_interval &b, const DevState &st, con
   if (given) {
     if (tid == 0) sh.node_delta = b.node_cpu_delta[n];
   } else {
-    if (tid < 128) red[tid] = red[tid] + red[tid + 128];
-    __syncthreads();
-    if (tid < 64) {
-      double x = red[tid] + red[tid + 64];
-#pragma unroll
-      for (int k = 32; k >= 1; k >>= 1) x = x + __shfl_down(x, k, 64);
-      if (tid == 0) sh.node_delta = x;
-    }
+    const double x = block_tree_sum(red, tid);
+    if (tid == 0) sh.node_delta = x;
   }
   __syncthreads();
-  if (tid == 0) {  // node scalars of the new snapshot (as the fast path)
-    const bool first = sh.first != 0;
-    st.node_ts[n] = b.node_ts_ns[n];
-    st.node_has_prev[n] = 1u;
-    st.node_usage_ratio[n] = first ? 0.0 : b.node_usage_ratio[n];
-    st.node_cpu_delta[n] = sh.node_delta;
-    st.node_status[n] = first ? KACC_NODE_FIRST_READ : KACC_NODE_OK;
-  }
+  if (tid == 0) store_node_scalars(st, n, sh.first != 0, sh.node_delta, b.node_ts_ns[n], b.node_usage_ratio[n]);
 }
 
 // The chunk items of every big node of a layout, once for all the intervals of a
@@ -2734,6 +2076,10 @@ __device__ __forceinline__ void node_params_to_lds(const DevState &st, uint32_t 
   }
 }
 
+// chunk_kernel keeps its own text of the rules of kacc_node.hpp (agg_segment, clamp_segment, pod_sum,
+// store_agg_cpu, load_agg_prev, group_is_contiguous, load_prev_or_zero, aggregate_out): as calls of
+// them it took 6-15 more VGPRs and lost a wave per SIMD at Z = 1, 2, 3 and 6 (119 -> 125 VGPRs at
+// Z = 4, the same occupancy step).  A change to one of those rules is made here too.
 template <int Z, int V>
 __global__ __launch_bounds__(kChunkThreads, (Z > 4 ? 2 : KACC_CHUNK_WAVES)) void chunk_kernel(const kacc_interval b,
                                                                            const DevState st) {
@@ -2830,7 +2176,7 @@ __global__ __launch_bounds__(kChunkThreads, (Z > 4 ? 2 : KACC_CHUNK_WAVES)) void
 #pragma unroll
       for (int u = 0; u < kR; ++u) {
         const uint64_t sl = w[u] & KACC_SLOT_MASK;
-        if constexpr (kT) {
+        if constexpr (kT) {  // mirrors group_is_contiguous, then load_prev_or_zero (kacc_node.hpp)
           const uint64_t s0 = uniform_u32(static_cast<uint32_t>(sl));
           const bool mine = (utid + u * kThreads) < rows && sl == s0 + (tid & 63) &&
                             s0 + 64 <= st.proc_slots;
@@ -2849,6 +2195,7 @@ __global__ __launch_bounds__(kChunkThreads, (Z > 4 ? 2 : KACC_CHUNK_WAVES)) void
       }
     }
     // aggregate j of this chunk: containers [cb, ce), VMs [vb, ve), pods [qb, qe)
+    // (mirrors agg_role / agg_segment of kacc_node.hpp in absolute indices)
     const uint32_t ctr_rows_end = rg.c1 > rg.c0 ? b.ctr_proc_end[rg.c1 - 1] : rg.p0;
     auto agg = [&](uint32_t j, uint32_t &beg, uint32_t &end, uint32_t &wd) -> uint32_t {
       if (j < nca) {
@@ -2915,7 +2262,7 @@ __global__ __launch_bounds__(kChunkThreads, (Z > 4 ? 2 : KACC_CHUNK_WAVES)) void
     // ---- C: owned containers / VMs (informer.go:223-273) ------------------------
     auto segment = [&](uint32_t role, uint32_t beg, uint32_t end, uint32_t wd, bool ok,
                        double &total) -> double {
-      if (beg < rg.p0 || end < beg || end > rg.p1) {
+      if (beg < rg.p0 || end < beg || end > rg.p1) {  // mirrors clamp_segment (kacc_node.hpp)
         raise_err(st.err, kErrOffsets);
         beg = max(min(beg, rg.p1), rg.p0);
         end = max(min(end, rg.p1), beg);
@@ -2957,13 +2304,13 @@ __global__ __launch_bounds__(kChunkThreads, (Z > 4 ? 2 : KACC_CHUNK_WAVES)) void
     bool defer = false;
     if (a_role == 3) {
       uint32_t beg = a_beg, end = a_end;
-      if (beg < rg.c0 || end < beg || end > rg.c1) {
+      if (beg < rg.c0 || end < beg || end > rg.c1) {  // mirrors clamp_segment (kacc_node.hpp)
         raise_err(st.err, kErrOffsets);
         beg = max(min(beg, rg.c1), rg.c0);
         end = max(min(end, rg.c1), beg);
       }
       if (end <= ce && end - cb <= static_cast<uint32_t>(kThreads) && beg >= cb) {
-        for (uint32_t c = beg - cb; c < end - cb; ++c) {
+        for (uint32_t c = beg - cb; c < end - cb; ++c) {  // mirrors pod_sum (kacc_node.hpp)
           a_delta = a_delta + s_cd[c];
           a_total = a_total + s_ct[c];  // quirk: the container's running total
         }
@@ -3072,11 +2419,11 @@ __global__ __launch_bounds__(kBlock) void pod_kernel(const kacc_interval b, cons
       continue;
     }
     const NodeRanges rg = node_ranges(b, st, n, 1);
-    uint32_t beg = q == rg.q0 ? rg.c0 : b.pod_ctr_end[q - 1];
-    uint32_t end = b.pod_ctr_end[q];
-    beg = max(min(beg, rg.c1), rg.c0);  // offsets were checked by chunk_kernel
+    uint32_t beg, end, w;
+    agg_segment(b, rg, 3u, q - rg.q0, beg, end, w);
+    // mirrors clamp_segment (kacc_node.hpp) without its report, as before: chunk_kernel checked
+    beg = max(min(beg, rg.c1), rg.c0);
     end = max(min(end, rg.c1), beg);
-    const uint32_t w = b.pod_slot[q];
     const uint64_t sl = w & KACC_SLOT_MASK;  // < pod_slots (checked before deferral)
     uint64_t prev[Z];
     load_row<Z>(st.pod_energy, pod_row(sl), prev);
@@ -3088,8 +2435,7 @@ __global__ __launch_bounds__(kBlock) void pod_kernel(const kacc_interval b, cons
       delta = delta + st.ctr_cpu_delta[cs];
       total = total + st.ctr_cpu_total[cs];
     }
-    st.pod_cpu_delta[sl] = delta;
-    st.pod_cpu_total[sl] = total;
+    store_agg_cpu(st, 3u, sl, delta, total);
     // this lane's node parameters (per lane: deferred pods of many nodes)
     Attr<Z> a;
     a.nd = st.node_cpu_delta[n];
@@ -3107,12 +2453,7 @@ __global__ __launch_bounds__(kBlock) void pod_kernel(const kacc_interval b, cons
       if (ok && a.aP[z] != 0) a.live |= 1u << z;
       if (ok && (a.first ? a.aP[z] : pw) != 0) a.live_pod |= 1u << z;
     }
-    uint64_t E[Z];
-    double P[Z];
-    attribute_row<Z>(a, a.live_pod, delta, (w & KACC_SLOT_NEW) != 0, prev, E, P);
-    store_row<Z, kNT, uint64_t>(st.pod_energy, pod_row(sl), E);
-    store_row<Z, kNT, double>(st.pod_power, pod_row(sl), P);
-    export_pod<Z>(b, q, E, P, st.err);
+    aggregate_out<Z, kNT>(b, st, a, 3u, w, true, delta, prev, n, q);
   }
 }
 
@@ -3346,29 +2687,42 @@ void launch_small(const kacc_interval &b, const kacc::DevState &s, hipStream_t s
     KACC_LAUNCH((kacc::small_kernel<Z, false>), dim3(grid), dim3(64 * kacc::kSmallWaves), 0, st, b, s);
 }
 
+// The big nodes' launches behind an interval's node kernel: none when the caller promised that
+// every node fits it.
+template <int Z, int V>
+void launch_big_nodes(const kacc_interval &b, const kacc::DevState &s, hipStream_t st) {
+  if (b.flags & (KACC_F_FAST_NODES | KACC_F_SMALL_NODES)) return;
+  const uint32_t chunk_grid = std::min<uint32_t>(s.item_cap, kacc::kChunkGrid);
+  KACC_LAUNCH((kacc::chunk_kernel<Z, V>), dim3(chunk_grid), dim3(kacc::kChunkThreads), 0, st, b, s);
+  KACC_LAUNCH((kacc::pod_kernel<Z, V>), dim3(kacc::kPodGrid), dim3(kacc::kBlock), 0, st, b, s);
+}
+
 template <int Z, int V>
 void launch_zv(const kacc_interval &b, const kacc::DevState &s, hipStream_t st) {
   if (V == 0 && (b.flags & KACC_F_SMALL_NODES)) return launch_small<Z>(b, s, st);
   KACC_LAUNCH((kacc::interval_kernel<Z, V>), dim3(b.n_nodes), dim3(kacc::kTpb<V>),
               KACC_FAST_EXTRA_LDS, st, b, s);
-  if (b.flags & (KACC_F_FAST_NODES | KACC_F_SMALL_NODES)) return;
-  const uint32_t chunk_grid = std::min<uint32_t>(s.item_cap, kacc::kChunkGrid);
-  KACC_LAUNCH((kacc::chunk_kernel<Z, V>), dim3(chunk_grid), dim3(kacc::kChunkThreads), 0, st,
-                     b, s);
-  KACC_LAUNCH((kacc::pod_kernel<Z, V>), dim3(kacc::kPodGrid), dim3(kacc::kBlock), 0, st, b, s);
+  launch_big_nodes<Z, V>(b, s, st);
+}
+
+// The kernels are compiled per zone count (1 .. KACC_MAX_ZONES, checked by kacc_create):
+// f(std::integral_constant<int, Z>) for a context's Z.
+template <typename F>
+void with_zones(uint32_t Z, F &&f) {
+  switch (Z) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 5: f(std::integral_constant<int, 5>{}); break;
+    case 6: f(std::integral_constant<int, 6>{}); break;
+    case 7: f(std::integral_constant<int, 7>{}); break;
+    default: f(std::integral_constant<int, 8>{}); break;
+  }
 }
 
 void launch(uint32_t Z, const kacc_interval &b, const kacc::DevState &s, hipStream_t st) {
-  switch (Z) {
-    case 1: launch_zv<1, 0>(b, s, st); break;
-    case 2: launch_zv<2, 0>(b, s, st); break;
-    case 3: launch_zv<3, 0>(b, s, st); break;
-    case 4: launch_zv<4, 0>(b, s, st); break;
-    case 5: launch_zv<5, 0>(b, s, st); break;
-    case 6: launch_zv<6, 0>(b, s, st); break;
-    case 7: launch_zv<7, 0>(b, s, st); break;
-    default: launch_zv<8, 0>(b, s, st); break;
-  }
+  with_zones(Z, [&](auto z) { launch_zv<decltype(z)::value, 0>(b, s, st); });
 }
 
 // timing ablations (Z = 4 only): see kacc::kVar*
@@ -3469,24 +2823,12 @@ template <int Z>
 void launch_fused(const kacc_interval &b, const kacc::DevState &s, const kacc::SumsArgs &sa, hipStream_t st) {
   KACC_LAUNCH((kacc::interval_sums_kernel<Z, 0>), dim3(b.n_nodes + sa.node_blocks + sa.ns_blocks),
               dim3(kacc::kTpb<0>), KACC_FAST_EXTRA_LDS, st, b, s, sa);
-  if (b.flags & (KACC_F_FAST_NODES | KACC_F_SMALL_NODES)) return;
-  const uint32_t chunk_grid = std::min<uint32_t>(s.item_cap, kacc::kChunkGrid);
-  KACC_LAUNCH((kacc::chunk_kernel<Z, 0>), dim3(chunk_grid), dim3(kacc::kChunkThreads), 0, st, b, s);
-  KACC_LAUNCH((kacc::pod_kernel<Z, 0>), dim3(kacc::kPodGrid), dim3(kacc::kBlock), 0, st, b, s);
+  launch_big_nodes<Z, 0>(b, s, st);
 }
 
 void launch_fused_z(uint32_t Z, const kacc_interval &b, const kacc::DevState &s, const kacc::SumsArgs &sa,
                     hipStream_t st) {
-  switch (Z) {
-    case 1: launch_fused<1>(b, s, sa, st); break;
-    case 2: launch_fused<2>(b, s, sa, st); break;
-    case 3: launch_fused<3>(b, s, sa, st); break;
-    case 4: launch_fused<4>(b, s, sa, st); break;
-    case 5: launch_fused<5>(b, s, sa, st); break;
-    case 6: launch_fused<6>(b, s, sa, st); break;
-    case 7: launch_fused<7>(b, s, sa, st); break;
-    default: launch_fused<8>(b, s, sa, st); break;
-  }
+  with_zones(Z, [&](auto z) { launch_fused<decltype(z)::value>(b, s, sa, st); });
 }
 
 // [p, p + bytes) and [q, q + bytes2) share a byte
@@ -3721,17 +3063,18 @@ int stage_batches(kacc_ctx *ctx, const kacc_interval *b, uint32_t K, hipStream_t
 template <int V>
 void launch_carry(uint32_t Z, bool medium, const kacc_interval *d_b, uint32_t K, uint32_t n_nodes,
                   const kacc::DevState &s, hipStream_t st) {
-  if (medium) {
-    if (Z == 1)
-      KACC_LAUNCH((kacc::intervals_carry_kernel<1, V, 256>), dim3(n_nodes), dim3(256), 0, st, d_b, K, s);
+  // compiled for Z = 1 and 2 only (kCarryMaxZ; kacc_run_intervals checks): no with_zones here
+  auto go = [&](auto z) {
+    constexpr int kZ = decltype(z)::value;
+    if (medium)
+      KACC_LAUNCH((kacc::intervals_carry_kernel<kZ, V, 256>), dim3(n_nodes), dim3(256), 0, st, d_b, K, s);
     else
-      KACC_LAUNCH((kacc::intervals_carry_kernel<2, V, 256>), dim3(n_nodes), dim3(256), 0, st, d_b, K, s);
-  } else {
-    if (Z == 1)
-      KACC_LAUNCH((kacc::intervals_carry_kernel<1, V, 512>), dim3(n_nodes), dim3(512), 0, st, d_b, K, s);
-    else
-      KACC_LAUNCH((kacc::intervals_carry_kernel<2, V, 512>), dim3(n_nodes), dim3(512), 0, st, d_b, K, s);
-  }
+      KACC_LAUNCH((kacc::intervals_carry_kernel<kZ, V, 512>), dim3(n_nodes), dim3(512), 0, st, d_b, K, s);
+  };
+  if (Z == 1)
+    go(std::integral_constant<int, 1>{});
+  else
+    go(std::integral_constant<int, 2>{});
 }
 
 void launch_intervals(uint32_t Z, bool medium, const kacc_interval *d_b, uint32_t K, uint32_t n_nodes,
@@ -4363,16 +3706,8 @@ int kacc_namespace_totals(kacc_ctx *ctx, uint32_t n_ns, const uint32_t *off, con
   KACC_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
   (void)hipGetLastError();  // clear a stale error of an earlier call
-  switch (ctx->cfg.zones) {
-    case 1: launch_ns<1>(n_ns, off, slots, ctx, out_energy, out_power, st); break;
-    case 2: launch_ns<2>(n_ns, off, slots, ctx, out_energy, out_power, st); break;
-    case 3: launch_ns<3>(n_ns, off, slots, ctx, out_energy, out_power, st); break;
-    case 4: launch_ns<4>(n_ns, off, slots, ctx, out_energy, out_power, st); break;
-    case 5: launch_ns<5>(n_ns, off, slots, ctx, out_energy, out_power, st); break;
-    case 6: launch_ns<6>(n_ns, off, slots, ctx, out_energy, out_power, st); break;
-    case 7: launch_ns<7>(n_ns, off, slots, ctx, out_energy, out_power, st); break;
-    default: launch_ns<8>(n_ns, off, slots, ctx, out_energy, out_power, st); break;
-  }
+  with_zones(ctx->cfg.zones,
+             [&](auto z) { launch_ns<decltype(z)::value>(n_ns, off, slots, ctx, out_energy, out_power, st); });
   KACC_HIP(ctx, hipGetLastError());
   return KACC_OK;
 }
@@ -4407,20 +3742,10 @@ int kacc_internal_export_partials(kacc_ctx *ctx, uint32_t n_ns, const uint32_t *
   const kacc::NodeTotalsArgs na = node_totals_args(ctx, live, node_export, node_energy, node_power);
   if (!n_ns && !node_blocks) return KACC_OK;
   (void)hipGetLastError();
-#define KACC_PARTIALS(Z_)                                                                                  \
-  launch_cluster_partials<Z_>(n_ns, off, slots, ctx, out_energy, out_power, na, node_blocks, st, pod_export, \
-                              n_pods)
-  switch (ctx->cfg.zones) {
-    case 1: KACC_PARTIALS(1); break;
-    case 2: KACC_PARTIALS(2); break;
-    case 3: KACC_PARTIALS(3); break;
-    case 4: KACC_PARTIALS(4); break;
-    case 5: KACC_PARTIALS(5); break;
-    case 6: KACC_PARTIALS(6); break;
-    case 7: KACC_PARTIALS(7); break;
-    default: KACC_PARTIALS(8); break;
-  }
-#undef KACC_PARTIALS
+  with_zones(ctx->cfg.zones, [&](auto z) {
+    launch_cluster_partials<decltype(z)::value>(n_ns, off, slots, ctx, out_energy, out_power, na, node_blocks, st,
+                                                pod_export, n_pods);
+  });
   KACC_HIP(ctx, hipGetLastError());
   return KACC_OK;
 }
@@ -4435,20 +3760,11 @@ int kacc_run_export_sums(kacc_ctx *ctx, const kacc_export_sums *x, void *stream)
   KACC_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
   (void)hipGetLastError();
-#define KACC_XSUMS(Z_)                                                                                        \
-  launch_cluster_partials<Z_>(sa.n_ns, sa.off, sa.ordered ? nullptr : sa.rows, ctx, sa.out_e, sa.out_p, sa.na, \
-                              sa.node_blocks, st, sa.pe, sa.n_pods, sa.ordered != 0)
-  switch (ctx->cfg.zones) {
-    case 1: KACC_XSUMS(1); break;
-    case 2: KACC_XSUMS(2); break;
-    case 3: KACC_XSUMS(3); break;
-    case 4: KACC_XSUMS(4); break;
-    case 5: KACC_XSUMS(5); break;
-    case 6: KACC_XSUMS(6); break;
-    case 7: KACC_XSUMS(7); break;
-    default: KACC_XSUMS(8); break;
-  }
-#undef KACC_XSUMS
+  with_zones(ctx->cfg.zones, [&](auto z) {
+    launch_cluster_partials<decltype(z)::value>(sa.n_ns, sa.off, sa.ordered ? nullptr : sa.rows, ctx, sa.out_e,
+                                                sa.out_p, sa.na, sa.node_blocks, st, sa.pe, sa.n_pods,
+                                                sa.ordered != 0);
+  });
   KACC_HIP(ctx, hipGetLastError());
   return KACC_OK;
 }
@@ -4516,16 +3832,10 @@ int kacc_internal_derived_power(kacc_ctx *ctx, int t, uint64_t first, uint64_t c
   const dim3 grid(static_cast<uint32_t>(std::min<uint64_t>((slots + per_block - 1) / per_block, 0x7fffffffull)));
   const kacc::ProcDerive d = kacc_derive(ctx, static_cast<kacc_kind>(kind));
   (void)hipGetLastError();
-  switch (Z) {
-    case 1: hipLaunchKernelGGL(kacc::proc_power_kernel<1>, grid, dim3(kacc::kBlock), 0, st, d, first, count, out); break;
-    case 2: hipLaunchKernelGGL(kacc::proc_power_kernel<2>, grid, dim3(kacc::kBlock), 0, st, d, first, count, out); break;
-    case 3: hipLaunchKernelGGL(kacc::proc_power_kernel<3>, grid, dim3(kacc::kBlock), 0, st, d, first, count, out); break;
-    case 4: hipLaunchKernelGGL(kacc::proc_power_kernel<4>, grid, dim3(kacc::kBlock), 0, st, d, first, count, out); break;
-    case 5: hipLaunchKernelGGL(kacc::proc_power_kernel<5>, grid, dim3(kacc::kBlock), 0, st, d, first, count, out); break;
-    case 6: hipLaunchKernelGGL(kacc::proc_power_kernel<6>, grid, dim3(kacc::kBlock), 0, st, d, first, count, out); break;
-    case 7: hipLaunchKernelGGL(kacc::proc_power_kernel<7>, grid, dim3(kacc::kBlock), 0, st, d, first, count, out); break;
-    default: hipLaunchKernelGGL(kacc::proc_power_kernel<8>, grid, dim3(kacc::kBlock), 0, st, d, first, count, out); break;
-  }
+  with_zones(Z, [&](auto z) {
+    hipLaunchKernelGGL(kacc::proc_power_kernel<decltype(z)::value>, grid, dim3(kacc::kBlock), 0, st, d, first, count,
+                       out);
+  });
   KACC_HIP(ctx, hipGetLastError());
   return KACC_OK;
 }
