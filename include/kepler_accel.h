@@ -47,7 +47,8 @@ extern "C" {
 #endif
 
 /* Still 6 with kacc_tracker_read, kacc_format_lines_dev, kacc_select_above,
- * kacc_group_sums and kacc_group_hist: they are new symbols only (no struct, no existing signature or result changed), so a client built
+ * kacc_group_sums, kacc_group_hist and kacc_group_quantiles: they are new
+ * symbols only (no struct, no existing signature or result changed), so a client built
  * against an earlier ABI-6 header runs unchanged.                              */
 #define KACC_ABI_VERSION 6u
 #define KACC_MAX_ZONES 8u
@@ -1281,6 +1282,88 @@ int kacc_group_hist(kacc_ctx *ctx, kacc_table t, uint32_t zone,
                     uint64_t *out_nan,           /* DEVICE [n_groups] or NULL                       */
                     uint64_t *out_unsummed,      /* DEVICE [n_groups] or NULL                       */
                     void *stream);
+
+/* ---- exact quantiles of the running workloads by group (ABI 6, additive) ----
+ * "The p99 of container power per runtime", `quantile by (label)`, and its two
+ * end points `min by` / `max by`: exact order statistics of ONE value per row
+ * over the RUNNING set, per caller-defined group, computed where the rows are.
+ * kacc_group_hist answers the same question only to the resolution of bounds
+ * the caller has to guess; this call needs none.  No reference call is replaced
+ * (Kepler exports every row; the quantile is the consumer's).
+ *
+ * TABLE, ZONE, ROWS, LISTING, VALIDITY, GROUP IDS — kacc_group_hist's to the
+ * letter: t is one of the eight workload tables, zone < Z, value(r) is the
+ * element of t at (row r's slot word & KACC_SLOT_MASK, zone) as kacc_table_read
+ * returns it (derived for processes, containers and VMs, stored for pods).  A
+ * row contributes iff its node is listed (node_mask, KACC_NODE_READ_ERROR, a
+ * row range inside [0, n_rows)), its slot is below the kind's capacity and
+ * group[r] < n_groups.  KACC_GROUP_NONE leaves the row out silently; any other
+ * id >= n_groups, a slot past the capacity or a node's row range outside the
+ * batch leaves those rows out, and each raises KACC_ERANGE at kacc_sync (bit
+ * 32768 of the device error word, "quantiles").  group == NULL requires
+ * n_groups == 1: every listed row is then in group 0.
+ *
+ * RANKED ROWS.  A contributing row whose power is a NaN is not ranked: it adds
+ * 1 to out_nan[g] and nothing else (an energy table has no NaN).
+ * out_count[g] = n is the number of ranked rows of group g.  They are ordered
+ * ascending by key(), the u64 sort key of the top lists: an energy is its own
+ * key; a power of ±0 has key 1<<63, p > 0 has bits | 1<<63, p < 0 has ~bits.
+ *
+ * THE RANKS are Prometheus' quantile().  phi is a HOST array of n_phi values in
+ * [0, 1], read before the call returns.  For phi[q] and n > 0:
+ *   rank   = phi[q] * (double)(n - 1)          (one IEEE multiply)
+ *   lower  = floor(rank),  upper = min(n - 1, lower + 1)
+ *   out_weight[g*n_phi + q] = rank - floor(rank)
+ *   out_lo[g*n_phi + q], out_hi[g*n_phi + q] = the value bits of the ranked rows
+ *       at positions lower and upper, recovered from the key: key >= 1<<63
+ *       gives bits = key & ~(1<<63) (either zero comes back as +0.0), otherwise
+ *       bits = ~key; for an energy table the bits are the µJ themselves.  So
+ *       phi = 0 is the group's minimum and phi = 1 its maximum, both in out_lo;
+ *   out_value[g*n_phi + q] = lo * (1 - weight) + hi * weight in f64, evaluated
+ *       in exactly that shape with no FMA, where lo and hi are the f64 µW of a
+ *       power table and (double) of the u64 µJ, correctly rounded, of an energy
+ *       table: the PromQL value.  With ±Inf operands the expression can be an
+ *       invalid operation (Inf * 0, Inf - Inf); IEEE 754 leaves that NaN's bits
+ *       to the platform, and this call gives 0xFFF8000000000000, the bits the
+ *       same expression has in C on an x86-64 host.
+ * A group without ranked rows (n == 0) has out_lo = out_hi = 0, out_weight = 0
+ * and out_value = the NaN with bits 0x7FF8000000000001; both counts are written.
+ *
+ * Every non-NULL output is written for every group and query (also with n_rows
+ * or n_nodes 0); outputs are overwritten, never accumulated into.  Every result
+ * is decided by integer counts and key comparisons alone, so two calls on the
+ * same inputs give the same bytes, whatever the tiling or the order of the rows.
+ *
+ * CLUSTER USE is not provided: an exact quantile of several shards is not a
+ * function of the shards' quantiles.  For a cluster-wide (approximate) quantile
+ * add the shards' kacc_group_hist words and interpolate.
+ *
+ * ERRORS — KACC_EINVAL, nothing launched: a NULL ctx / rows / row_off / phi, a
+ * NULL slot with n_rows > 0, a NULL group with n_groups != 1, a table that is
+ * not one of the eight, zone >= Z, n_phi outside 1 .. KACC_QUANT_MAX_PHI,
+ * n_groups outside 1 .. KACC_GROUP_MAX, n_groups * n_phi >
+ * KACC_QUANT_MAX_QUERIES, a phi that is NaN or outside [0, 1], n_nodes > the
+ * context's nodes, all six outputs NULL.
+ *
+ * Asynchronous on `stream` (NULL = the context's): nothing is read back, there
+ * is no device-wide synchronize, and the scratch memory is stream-ordered.
+ * Every index is clamped: no input faults.                                    */
+#define KACC_QUANT_MAX_PHI      8u        /* largest n_phi                     */
+#define KACC_QUANT_MAX_QUERIES  65536u    /* largest n_groups * n_phi          */
+int kacc_group_quantiles(kacc_ctx *ctx, kacc_table t, uint32_t zone,
+                         const kacc_top_rows *rows,  /* the kind's rows of the last interval batch      */
+                         const uint32_t *group,      /* DEVICE [n_rows], or NULL: every row in group 0  */
+                         uint32_t n_groups,
+                         const double *phi,          /* HOST [n_phi], each in [0, 1]; read before return */
+                         uint32_t n_phi,
+                         const uint32_t *node_mask,  /* DEVICE [n_nodes], nonzero = listed; NULL = all  */
+                         uint64_t *out_count,        /* DEVICE [n_groups]         or NULL               */
+                         uint64_t *out_nan,          /* DEVICE [n_groups]         or NULL               */
+                         uint64_t *out_lo,           /* DEVICE [n_groups * n_phi] or NULL: value bits   */
+                         uint64_t *out_hi,           /* DEVICE [n_groups * n_phi] or NULL: value bits   */
+                         double   *out_weight,       /* DEVICE [n_groups * n_phi] or NULL               */
+                         double   *out_value,        /* DEVICE [n_groups * n_phi] or NULL               */
+                         void *stream);
 
 /* Algorithmic HBM bytes of K consecutive intervals of these sizes: K times
  * kacc_interval_bytes, or (carried != 0: kacc_run_intervals' one-launch path,

@@ -59,6 +59,8 @@ KACC_GROUP_MAX = 65536  # largest n_groups
 KACC_GROUP_POWER_FRAC_BITS = 12  # out_power_fx: units of 2^-12 µW
 KACC_HIST_MAX_BOUNDS = 64  # kacc_group_hist: largest n_bounds
 KACC_HIST_MAX_BINS = 1 << 20  # largest n_groups * (n_bounds + 1)
+KACC_QUANT_MAX_PHI = 8  # kacc_group_quantiles: largest n_phi
+KACC_QUANT_MAX_QUERIES = 65536  # largest n_groups * n_phi
 KACC_TRACKER_READ_CLEAR = 0x1  # kacc_tracker_read: clear the listed nodes' trackers behind the read
 
 # kacc_table enum, in header order: (name, numpy dtype)
@@ -115,6 +117,7 @@ EXPORTS = [
     "kacc_select_above",
     "kacc_group_sums",
     "kacc_group_hist",
+    "kacc_group_quantiles",
     "kacc_zone_agg_create",
     "kacc_zone_agg_destroy",
     "kacc_zone_agg_read",
@@ -363,6 +366,8 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.kacc_group_sums.argtypes = ([c_void_p, c_int, POINTER(KaccTopRows), c_void_p, c_uint32] + [c_void_p] * 7)
     lib.kacc_group_hist.argtypes = ([c_void_p, c_int, c_uint32, POINTER(KaccTopRows), c_void_p, c_uint32, c_void_p,
                                      c_uint32] + [c_void_p] * 7)
+    lib.kacc_group_quantiles.argtypes = ([c_void_p, c_int, c_uint32, POINTER(KaccTopRows), c_void_p, c_uint32,
+                                          c_void_p, c_uint32] + [c_void_p] * 8)
     lib.kacc_last_error_copy.argtypes = [c_void_p, c_char_p, ctypes.c_size_t]
     lib.kacc_last_error_copy.restype = ctypes.c_size_t
     lib.kacc_create_multi.argtypes = [POINTER(c_int), c_int, POINTER(KaccConfig), POINTER(c_void_p),
@@ -789,6 +794,23 @@ class Accel:
                                              c_void_p(out_cum_ptr or None), c_void_p(out_sum_ptr or None),
                                              c_void_p(out_nan_ptr or None), c_void_p(out_unsummed_ptr or None),
                                              c_void_p(stream or None)))
+
+    def group_quantiles(self, table: str, zone: int, rows: KaccTopRows, group_ptr: int, n_groups: int, phi,
+                        node_mask_ptr: int = 0, out_count_ptr: int = 0, out_nan_ptr: int = 0, out_lo_ptr: int = 0,
+                        out_hi_ptr: int = 0, out_weight_ptr: int = 0, out_value_ptr: int = 0, stream: int = 0) -> None:
+        """kacc_group_quantiles: exact quantiles of `table`'s values in `zone` over the running workloads of
+        the batch, per group id of each row (device u32 [n_rows]; 0 = every row in group 0, n_groups 1).
+        `phi` is a sequence or array of f64 in [0, 1]; count and nan are u64 [n_groups], lo and hi (the
+        value bits at the lower and upper rank) u64 and weight and value f64 [n_groups * len(phi)]
+        (device pointers, each optional)."""
+        f = np.ascontiguousarray(phi, dtype=np.float64)
+        self._check(self.lib.kacc_group_quantiles(self.ctx, TABLE_INDEX[table], zone, ctypes.byref(rows),
+                                                  c_void_p(group_ptr or None), n_groups, c_void_p(f.ctypes.data),
+                                                  f.size, c_void_p(node_mask_ptr or None),
+                                                  c_void_p(out_count_ptr or None), c_void_p(out_nan_ptr or None),
+                                                  c_void_p(out_lo_ptr or None), c_void_p(out_hi_ptr or None),
+                                                  c_void_p(out_weight_ptr or None), c_void_p(out_value_ptr or None),
+                                                  c_void_p(stream or None)))
 
     def namespace_totals(self, n_ns: int, ns_pod_off_ptr: int, ns_pod_slot_ptr: int,
                          out_energy_ptr: int, out_power_ptr: int, stream: int = 0) -> None:

@@ -3329,11 +3329,11 @@ int kacc_sync(kacc_ctx *ctx, void *stream) {
     // every bit a library kernel raises (kacc_engine / join / format / tracker / ticks /
     // packer / cluster); any other bit has no writer in the library — a stray device
     // store into this word — and is named as such
-    constexpr uint32_t kKnown = 0x7fffu;
+    constexpr uint32_t kKnown = 0xffffu;
     if (err & ~kKnown)
       return fail(ctx, KACC_ERANGE, "device error word 0x%x holds bits no library kernel raises (0x%x): a stray "
                   "device store into the context's error word; known bits 0x%x", err, err & ~kKnown, err & kKnown);
-    return fail(ctx, KACC_ERANGE, "device range check failed (bits 0x%x: 1=node 2=offsets 4=slot 8=namespace 16=work list 32=oversized node under KACC_F_FAST_NODES 64=join key 128=join range 256=format lines 512=top list 1024=tracker capacity 2048=tracker read 4096=select 8192=group sums 16384=histogram)", err);
+    return fail(ctx, KACC_ERANGE, "device range check failed (bits 0x%x: 1=node 2=offsets 4=slot 8=namespace 16=work list 32=oversized node under KACC_F_FAST_NODES 64=join key 128=join range 256=format lines 512=top list 1024=tracker capacity 2048=tracker read 4096=select 8192=group sums 16384=histogram) (32768=quantiles)", err);
   }
   return KACC_OK;
 }

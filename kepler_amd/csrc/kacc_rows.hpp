@@ -1,6 +1,6 @@
 // The rows of an interval batch for the workload row queries - kacc_top.hip, kacc_select.hip,
-// kacc_group.hip, kacc_hist.hip (device and host helpers, not part of the public
-// ABI).  All four read the rows of the caller's last interval batch (kacc_top_rows) for one
+// kacc_group.hip, kacc_hist.hip, kacc_quant.hip (device and host helpers, not part
+// of the public ABI).  All five read the rows of the caller's last interval batch (kacc_top_rows) for one
 // workload kind and ask the same things: is the row listed, is its slot valid, what is its
 // value (an energy word, a stored pod power, or the derived ratio[slot] · ActivePower[node]
 // under the node's guard) or its Z-word record.  Here, once: the value rules, the row view, the
@@ -36,6 +36,11 @@ __host__ __device__ __forceinline__ uint64_t power_key(uint64_t b) {
   if (mag > 0x7ff00000u || (mag == 0x7ff00000u && lo != 0)) return 0;  // NaN
   if ((mag | lo) == 0) return 0x8000000000000000ull;                   // ±0
   return (hi >> 31) ? ~b : (b | 0x8000000000000000ull);
+}
+// The value bits a non-NaN key came from: an energy's are the key itself, a power's come back
+// through this inverse of power_key (either zero as +0.0).
+__host__ __device__ __forceinline__ uint64_t power_key_bits(uint64_t key) {
+  return (key >> 63) ? (key & 0x7fffffffffffffffull) : ~key;
 }
 // fx(p) of the header for the f64 with these bits; keep: finite and |p| < 2^50, else fx is 0.
 __device__ __forceinline__ uint64_t power_fx(uint64_t bits, bool &keep) {
