@@ -47,8 +47,8 @@ extern "C" {
 #endif
 
 /* Still 6 with kacc_tracker_read, kacc_format_lines_dev, kacc_select_above,
- * kacc_group_sums, kacc_group_hist and kacc_group_quantiles: they are new
- * symbols only (no struct, no existing signature or result changed), so a client built
+ * kacc_group_sums, kacc_group_hist, kacc_group_quantiles and kacc_group_top:
+ * they are new symbols only (no struct, no existing signature or result changed), so a client built
  * against an earlier ABI-6 header runs unchanged.                              */
 #define KACC_ABI_VERSION 6u
 #define KACC_MAX_ZONES 8u
@@ -1364,6 +1364,84 @@ int kacc_group_quantiles(kacc_ctx *ctx, kacc_table t, uint32_t zone,
                          double   *out_weight,       /* DEVICE [n_groups * n_phi] or NULL               */
                          double   *out_value,        /* DEVICE [n_groups * n_phi] or NULL               */
                          void *stream);
+
+/* ---- top consumers of the running workloads by group (ABI 6, additive) ------
+ * "The 5 hungriest pods of every namespace", "the 10 top processes per rack,
+ * per tenant, per comm": `topk by (label)(k, ...)` over the RUNNING set, one
+ * list per caller-defined group, selected where the rows are.  kacc_top_nodes
+ * answers it only when the group is the node, and kacc_top_fleet when there is
+ * one group; where they apply they are the faster calls (they stream a node's
+ * rows once and keep no per-row record), so use them there.  No reference call
+ * is replaced (Kepler exports every row; the ranking is the consumer's).
+ *
+ * TABLE, ZONE, ROWS, LISTING, VALIDITY, GROUP IDS — kacc_group_hist's to the
+ * letter: t is one of the eight workload tables, zone < Z, value(r) is the
+ * element of t at (row r's slot word & KACC_SLOT_MASK, zone) as kacc_table_read
+ * returns it (derived for processes, containers and VMs, stored for pods).  A
+ * row contributes iff its node is listed (node_mask, KACC_NODE_READ_ERROR, a
+ * row range inside [0, n_rows)), its slot is below the kind's capacity and
+ * group[r] < n_groups.  KACC_GROUP_NONE leaves the row out silently; any other
+ * id >= n_groups, a slot past the capacity or a node's row range outside the
+ * batch leaves those rows out, and each raises KACC_ERANGE at kacc_sync.  The
+ * bit of the device error word is 512, "top list": a per-group top list is a
+ * top list, so this call shares the bit with kacc_top_nodes / kacc_top_fleet.
+ * group == NULL requires n_groups == 1: every listed row is then in group 0.
+ *
+ * ORDER — kacc_top_*'s to the letter: the same u64 sort key, lists in
+ * DESCENDING key order, equal keys in ASCENDING batch row order.  A power that
+ * is a NaN has key 0 and is ranked last, as in the top lists; it is NOT dropped
+ * as in kacc_group_quantiles.  With n_g contributing rows in group g, the list
+ * of g is the first min(k, n_g) of them in that order, and
+ * out_count[g] = min(k, n_g).
+ *
+ * OUTPUTS.  Entry g*k + i is the i-th row of group g's list: out_row the batch
+ * row index, out_slot the row's slot (its slot word & KACC_SLOT_MASK;
+ * kacc_unpack takes it as it is), out_node the row's node, out_value the
+ * table's own value (µJ, or the bits of the f64 µW: a -0.0 stays -0.0, a NaN
+ * keeps its bits).  Entries past the count hold 0xffffffff in row, slot and
+ * node and 0 in value.  Every non-NULL output is written for every group (also
+ * with n_rows or n_nodes 0); outputs are overwritten, never accumulated into.
+ * Every result is decided by integer counts and comparisons of the unique
+ * (key, row) pair alone, so two calls on the same inputs give the same bytes,
+ * whatever the tiling; listing the rows of a node in another order changes the
+ * row indices and nothing else (between equal keys the lower row index wins).
+ *
+ * IDENTITIES:
+ *   - group == NULL, n_groups == 1, node_mask == NULL: kacc_top_fleet's five
+ *     outputs, byte for byte;
+ *   - group[r] = the node of r, n_groups == n_nodes: kacc_top_nodes' count,
+ *     row, slot and value;
+ *   - out_count[g] == min(k, kacc_group_sums' out_count[g]);
+ *   - an energy table: the first value of a non-empty group is
+ *     kacc_group_quantiles' out_lo at phi = 1.
+ *
+ * CLUSTER USE.  The top k of a union of shards is contained in the union of the
+ * shards' top-k lists: run the call on every shard and merge the shards' lists
+ * of a group by (key descending, shard order, row ascending), cut to k.  That
+ * merge of n_shards * n_groups * k entries is exact and is the caller's.
+ *
+ * ERRORS — KACC_EINVAL, nothing launched: a NULL ctx / rows / row_off, a NULL
+ * slot with n_rows > 0, a NULL group with n_groups != 1, a table that is not
+ * one of the eight, zone >= Z, k outside 1 .. KACC_TOP_MAX, n_groups outside
+ * 1 .. KACC_GROUP_MAX, n_groups * k > KACC_GROUP_TOP_MAX_ITEMS, n_nodes > the
+ * context's nodes, all five outputs NULL.
+ *
+ * Asynchronous on `stream` (NULL = the context's): nothing is read back, there
+ * is no device-wide synchronize, and the scratch memory (12 bytes per row and
+ * per output entry, about 1 KiB per group) is stream-ordered.  Every index is
+ * clamped: no input faults.                                                   */
+#define KACC_GROUP_TOP_MAX_ITEMS (1u << 20)   /* largest n_groups * k */
+int kacc_group_top(kacc_ctx *ctx, kacc_table t, uint32_t zone, uint32_t k,
+                   const kacc_top_rows *rows,   /* the kind's rows of the last interval batch     */
+                   const uint32_t *group,       /* DEVICE [n_rows], or NULL: every row in group 0 */
+                   uint32_t n_groups,
+                   const uint32_t *node_mask,   /* DEVICE [n_nodes], nonzero = listed; NULL = all */
+                   uint32_t *out_count,         /* DEVICE [n_groups]      or NULL */
+                   uint32_t *out_row,           /* DEVICE [n_groups * k]  or NULL: batch row      */
+                   uint32_t *out_slot,          /* DEVICE [n_groups * k]  or NULL */
+                   uint32_t *out_node,          /* DEVICE [n_groups * k]  or NULL */
+                   uint64_t *out_value,         /* DEVICE [n_groups * k]  or NULL: µJ / f64 bits  */
+                   void *stream);
 
 /* Algorithmic HBM bytes of K consecutive intervals of these sizes: K times
  * kacc_interval_bytes, or (carried != 0: kacc_run_intervals' one-launch path,

@@ -61,6 +61,7 @@ KACC_HIST_MAX_BOUNDS = 64  # kacc_group_hist: largest n_bounds
 KACC_HIST_MAX_BINS = 1 << 20  # largest n_groups * (n_bounds + 1)
 KACC_QUANT_MAX_PHI = 8  # kacc_group_quantiles: largest n_phi
 KACC_QUANT_MAX_QUERIES = 65536  # largest n_groups * n_phi
+KACC_GROUP_TOP_MAX_ITEMS = 1 << 20  # kacc_group_top: largest n_groups * k
 KACC_TRACKER_READ_CLEAR = 0x1  # kacc_tracker_read: clear the listed nodes' trackers behind the read
 
 # kacc_table enum, in header order: (name, numpy dtype)
@@ -118,6 +119,7 @@ EXPORTS = [
     "kacc_group_sums",
     "kacc_group_hist",
     "kacc_group_quantiles",
+    "kacc_group_top",
     "kacc_zone_agg_create",
     "kacc_zone_agg_destroy",
     "kacc_zone_agg_read",
@@ -368,6 +370,9 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
                                      c_uint32] + [c_void_p] * 7)
     lib.kacc_group_quantiles.argtypes = ([c_void_p, c_int, c_uint32, POINTER(KaccTopRows), c_void_p, c_uint32,
                                           c_void_p, c_uint32] + [c_void_p] * 8)
+    if hasattr(lib, "kacc_group_top"):  # KACC_LIB A/B builds of earlier sources lack it
+        lib.kacc_group_top.argtypes = ([c_void_p, c_int, c_uint32, c_uint32, POINTER(KaccTopRows), c_void_p, c_uint32]
+                                       + [c_void_p] * 7)
     lib.kacc_last_error_copy.argtypes = [c_void_p, c_char_p, ctypes.c_size_t]
     lib.kacc_last_error_copy.restype = ctypes.c_size_t
     lib.kacc_create_multi.argtypes = [POINTER(c_int), c_int, POINTER(KaccConfig), POINTER(c_void_p),
@@ -811,6 +816,19 @@ class Accel:
                                                   c_void_p(out_lo_ptr or None), c_void_p(out_hi_ptr or None),
                                                   c_void_p(out_weight_ptr or None), c_void_p(out_value_ptr or None),
                                                   c_void_p(stream or None)))
+
+    def group_top(self, table: str, zone: int, k: int, rows: KaccTopRows, group_ptr: int, n_groups: int,
+                  node_mask_ptr: int = 0, out_count_ptr: int = 0, out_row_ptr: int = 0, out_slot_ptr: int = 0,
+                  out_node_ptr: int = 0, out_value_ptr: int = 0, stream: int = 0) -> None:
+        """kacc_group_top: per group id of each row (device u32 [n_rows]; 0 = every row in group 0, n_groups
+        1), the min(k, rows) running workloads of the batch with the highest value of `table` in `zone`,
+        in kacc_top_*'s order: count u32 [n_groups]; row, slot and node u32 and value u64 (µJ, or the bits
+        of the f64 µW) [n_groups * k] (device pointers, each optional)."""
+        self._check(self.lib.kacc_group_top(self.ctx, TABLE_INDEX[table], zone, k, ctypes.byref(rows),
+                                            c_void_p(group_ptr or None), n_groups, c_void_p(node_mask_ptr or None),
+                                            c_void_p(out_count_ptr or None), c_void_p(out_row_ptr or None),
+                                            c_void_p(out_slot_ptr or None), c_void_p(out_node_ptr or None),
+                                            c_void_p(out_value_ptr or None), c_void_p(stream or None)))
 
     def namespace_totals(self, n_ns: int, ns_pod_off_ptr: int, ns_pod_slot_ptr: int,
                          out_energy_ptr: int, out_power_ptr: int, stream: int = 0) -> None:
