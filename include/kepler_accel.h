@@ -595,7 +595,15 @@ int kacc_gather_pods(kacc_cluster *c, const uint32_t *n_pods, const uint32_t *co
  * KACC_ERANGE at kacc_sync; the affected rows get slot word 0xffffffff (of
  * two rows carrying one ID, which one keeps a slot is unspecified: the whole
  * call is reported as failed).  A PID node with <= 2730 slots given more than
- * 3072 rows fails whole: every row 0xffffffff, its map unchanged.            */
+ * 3072 rows fails whole: every row 0xffffffff, its map unchanged.
+ * A PID node with <= 2730 slots keeps each PID in one of two 4-bucket groups
+ * of its table (two-choice placement).  A PID set that table cannot hold (nine
+ * live PIDs sharing one pair of groups, say; random PIDs never get there at
+ * load <= 2/3) fails the call with KACC_ERANGE too, but marks no row: making
+ * room moves older PIDs, and the one left without a bucket is a live one, not
+ * the new one.  That node's map and the slot words it gives are then
+ * unspecified until kacc_slotmap_reset(); the call's other nodes are served
+ * as usual.                                                                  */
 typedef enum kacc_kind {
   KACC_KIND_PROC = 0, /* key: uint32_t PID — process.go:120 StringID        */
   KACC_KIND_CTR = 1,  /* key: uint64_t ID of the container ID string        */

@@ -37,6 +37,15 @@ int kacc_debug_join_variant(kacc_slotmap *m, uint32_t n_rows, const uint32_t *ro
  * 4 LDS-only barriers, 8 duplicates found by the insert, 16 shared scan barrier);
  * -1 = production.  Every variant computes the same results.  Returns the old value. */
 int kacc_debug_set_join_variant(int variant);
+/* One node's table of live IDs as it stands (tests check it against the table rules).
+ * Synchronous: waits for the map's device, then copies.  *buckets = the node's bucket
+ * count H; when cap >= H, key[b] / slot[b] = bucket b's key and stored (node-relative)
+ * slot for b < H, whatever the storage format (6-B PID buckets of a small node, packed
+ * PID entries, key array + slot array of the 64-bit kinds); empty and tombstone keys
+ * are widened to KACC_KEY_EMPTY / KACC_KEY_TOMB, whose slots mean nothing.
+ * KACC_EINVAL: NULL argument, node >= the map's nodes, or cap < H (*buckets is set). */
+int kacc_debug_slotmap_node(kacc_slotmap *m, uint32_t node, uint32_t cap, uint32_t *buckets, uint64_t *key,
+                            uint32_t *slot);
 
 #ifdef __cplusplus
 }

@@ -1704,6 +1704,45 @@ int kacc_debug_set_join_variant(int variant) {
   return prev;
 }
 
+int kacc_debug_slotmap_node(kacc_slotmap *m, uint32_t node, uint32_t cap, uint32_t *buckets, uint64_t *key,
+                            uint32_t *slot) {
+  if (!m || !buckets || !key || !slot) return KACC_EINVAL;
+  kacc_ctx *ctx = m->ctx;
+  if (node >= m->n_nodes) return kacc_fail(ctx, KACC_EINVAL, "slot map dump: node %u of %u", node, m->n_nodes);
+  KACC_HIP(ctx, hipSetDevice(m->device));
+  KACC_HIP(ctx, hipDeviceSynchronize());
+  uint64_t hoff[2];
+  KACC_HIP(ctx, hipMemcpy(hoff, m->d_hoff + node, sizeof(hoff), hipMemcpyDeviceToHost));
+  const uint64_t hb = hoff[0];
+  const uint32_t H = static_cast<uint32_t>(hoff[1] - hoff[0]);
+  *buckets = H;
+  if (cap < H) return kacc_fail(ctx, KACC_EINVAL, "slot map dump: node %u has %u buckets, cap %u", node, H, cap);
+  std::vector<uint64_t> ent(H);  // the node's 8H-byte region of d_ent
+  KACC_HIP(ctx, hipMemcpy(ent.data(), m->d_ent + hb, 8ull * H, hipMemcpyDeviceToHost));
+  if (m->kind != KACC_KIND_PROC) {  // the keys; the slots in their own array
+    KACC_HIP(ctx, hipMemcpy(slot, m->d_slots + hb, 4ull * H, hipMemcpyDeviceToHost));
+    std::memcpy(key, ent.data(), 8ull * H);
+    return KACC_OK;
+  }
+  const auto widen = [](uint32_t k) -> uint64_t {
+    return k == 0xffffffffu ? KACC_KEY_EMPTY : k == 0xfffffffeu ? KACC_KEY_TOMB : k;
+  };
+  if (H <= kacc::join::kLdsBuckets && m->fmt != 0) {  // 6-B buckets: H u32 keys, then H u16 slots
+    const uint32_t *k32 = reinterpret_cast<const uint32_t *>(ent.data());
+    const uint16_t *s16 = reinterpret_cast<const uint16_t *>(k32 + H);
+    for (uint32_t b = 0; b < H; ++b) {
+      key[b] = widen(k32[b]);
+      slot[b] = s16[b];
+    }
+  } else {  // packed key << 32 | slot
+    for (uint32_t b = 0; b < H; ++b) {
+      key[b] = widen(static_cast<uint32_t>(ent[b] >> 32));
+      slot[b] = static_cast<uint32_t>(ent[b]);
+    }
+  }
+  return KACC_OK;
+}
+
 }  // extern "C"
 
 static int slot_join(kacc_slotmap *m, uint32_t n_rows, const uint32_t *row_off, const void *keys,
