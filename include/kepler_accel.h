@@ -1451,6 +1451,139 @@ int kacc_group_top(kacc_ctx *ctx, kacc_table t, uint32_t zone, uint32_t k,
                    uint64_t *out_value,         /* DEVICE [n_groups * k]  or NULL: µJ / f64 bits  */
                    void *stream);
 
+/* ---- energy over a window, summed by group (ABI 6, additive) -----------------
+ * "Joules by namespace over the last hour": PromQL's
+ *     sum by (label)(increase(kepler_*_joules_total[w]))
+ * the query behind every Kepler dashboard, bill and carbon report, computed
+ * where the counters are.  The row queries above answer a question about one
+ * instant of the running set; this is their time dimension.  No reference call
+ * is replaced: Kepler exports the counters - and its terminated workloads, so
+ * that their last joules reach such a query
+ * (internal/monitor/terminated_resource_tracker.go, process.go:87-99) - and
+ * leaves the increase to PromQL.
+ *
+ * STATE.  One window serves one workload kind and n_groups groups.  With S the
+ * kind's slot capacity and Z the context's zones it holds, on the device:
+ *   base          u64 [S*Z] (dense, also for the pods): the slot's EnergyTotal[z]
+ *                 at the window's start; 0 for a workload born inside the window;
+ *   slot_group    u32 [S]: the group of the slot's workload, KACC_GROUP_NONE = the
+ *                 slot is not in the window;
+ *   retired       u64 [G*Z]: per group, the energy that the workloads which
+ *                 terminated inside the window used inside it;
+ *   retired_count u32 [G]: per group, the number of those workloads.
+ * A fresh window has base 0, slot_group KACC_GROUP_NONE and retired 0.  The
+ * state costs S * (8Z + 4) bytes (20M process slots at Z = 4: 720 MB);
+ * KACC_ENOMEM, with that figure in the message, when it does not fit.
+ *
+ * kacc_window_step() - once per interval, in kacc_tracker_add's place: after the
+ * kacc_slot_join that produced rows->slot and the terminated segments and BEFORE
+ * the context's next interval, on the same stream or with an event the
+ * interval's stream waits for - for kacc_tracker_add's reason: the next
+ * interval rewrites the terminated slots' totals (at once under
+ * KACC_JOIN_REUSE_TERMINATED).  Two phases; for every slot (a) happens before
+ * (b), so one call both retires a slot and hands it to a newcomer.
+ *   (a) RETIRE - skipped when term_count is NULL (m and term_slot may then be
+ *       NULL too).  For node n of the slot map and i < term_count[n], with
+ *       s = term_slot[slot_off[n] + i] (the join's segments) and
+ *       g = slot_group[s]: when g < G, retired[g*Z+z] += E[s,z] - base[s,z]
+ *       mod 2^64 for every z and retired_count[g] += 1; in every case
+ *       slot_group[s] = KACC_GROUP_NONE (a slot listed twice retires once).  A
+ *       slot at or past the capacity is left out; a term_count[n] above the
+ *       node's segment leaves the node's whole list out; each raises
+ *       KACC_ERANGE.
+ *   (b) ADOPT - for every LISTED row r whose slot word has KACC_SLOT_NEW, with
+ *       s = word & KACC_SLOT_MASK: base[s,:] = 0 and slot_group[s] = group[r].
+ *       "Listed" is the row queries' rule without a mask: the row's node has no
+ *       KACC_NODE_READ_ERROR in rows->node_status and its row range is inside
+ *       the batch.  The rows of a skipped node are never adopted: the join
+ *       leaves their slot words untouched, so they may carry a stale
+ *       KACC_SLOT_NEW.  group == NULL requires n_groups == 1 and stores 0.  An
+ *       id at or past G other than KACC_GROUP_NONE is stored as KACC_GROUP_NONE
+ *       and raises KACC_ERANGE; so does a listed row whose slot is at or past
+ *       the capacity (it is left out), and a node whose row range is not inside
+ *       the batch (its rows are not listed).  With KACC_WINDOW_ASSIGN_ALL every
+ *       listed row stores slot_group[s] = group[r] - to attach a window to a
+ *       fleet that is already running, or to relabel; base is still reset for
+ *       the NEW rows only.
+ *
+ * kacc_window_mark() starts or restarts the window for the whole context:
+ * base[s,z] = E[s,z] for every slot of the kind, retired and retired_count = 0,
+ * slot_group stays.  It needs no rows: a node skipped by a read error keeps its
+ * last good totals in the tables, so the copy is right for it too.  Order it as
+ * a read: after an interval, before the next.
+ *
+ * kacc_window_read().  For every listed row r - kacc_group_sums' rule:
+ * node_mask, node status, row range - with slot s below the capacity, and
+ * inc[z] = E[s,z] - base[s,z] mod 2^64:
+ *   out_row[r*Z+z]       inc[z]; every other row of the batch gets 0, so every
+ *                        element is written: the dense u64 µJ array
+ *                        kacc_format_lines_dev(is_energy = 1) takes.  At Z = 4
+ *                        it is written with 16-byte stores: any 8-byte
+ *                        aligned pointer is valid, a 16-byte aligned one
+ *                        (every hipMalloc pointer) gives the full rate;
+ *   out_count[g]         the listed rows with slot_group[s] == g;
+ *   out_running[g*Z+z]   the sum of their inc[z] mod 2^64;
+ *   out_retired[g*Z+z], out_retired_count[g]
+ *                        the window's accumulators.  They are NOT masked:
+ *                        node_mask applies to the running part only (a
+ *                        terminated workload keeps no node in the window);
+ *   out_total[g*Z+z]     out_running + out_retired mod 2^64.
+ * Every non-NULL output is written for every group (also with n_rows or
+ * n_nodes 0); outputs are overwritten, never accumulated into.  A listed row
+ * with a slot at or past the capacity is left out (its out_row is 0), and so
+ * are the rows of a node whose row range is not inside the batch; each raises
+ * KACC_ERANGE.  Every output is an integer sum: the same bytes for any tiling,
+ * any row order, any split into shards and any number of GPUs; all outputs add
+ * word by word through the u64 vector of kacc_allreduce_sums.
+ *
+ * IDENTITIES: a read straight after a mark gives out_running and out_row 0; a
+ * window stepped with KACC_WINDOW_ASSIGN_ALL from the first interval on and
+ * never marked gives kacc_group_sums' out_count and out_energy as out_count and
+ * out_running (no read errors); out_total over a window is the sum of the
+ * out_total of its intervals, each read and marked on its own.
+ *
+ * kacc_window_download() - synchronous (tests, checkpoints): base and
+ * slot_group of `count` slots from slot `first` into HOST arrays.
+ *
+ * ERRORS - KACC_EINVAL, nothing launched: a NULL handle, context or out; an
+ * unknown kind; n_groups outside 1 .. KACC_GROUP_MAX; a NULL rows / row_off, a
+ * NULL slot with n_rows > 0; n_nodes > the context's nodes; a NULL group with
+ * n_groups != 1; unknown flag bits; term_count without m or term_slot; a slot
+ * map of another kind or context; all six outputs NULL; a download range past
+ * the capacity.  Device errors raise KACC_ERANGE at kacc_sync with bit 8192,
+ * "group sums", of the device error word: a window's group sum is a group sum.
+ * Every index is clamped: no input faults, and every other word stays exact.
+ *
+ * step, mark and read are asynchronous on `stream` (NULL = the context's):
+ * nothing is read back, there is no device-wide synchronize, and the scratch
+ * memory is stream-ordered.                                                   */
+typedef struct kacc_window kacc_window;
+#define KACC_WINDOW_ASSIGN_ALL 0x1u /* step: every listed row stores its group id */
+int kacc_window_create(kacc_ctx *ctx, kacc_kind kind, uint32_t n_groups, kacc_window **out);
+void kacc_window_destroy(kacc_window *w); /* safe before or after kacc_destroy(ctx) */
+int kacc_window_step(kacc_window *w,
+                     const kacc_top_rows *rows,   /* the kind's rows of the batch the join just served */
+                     const uint32_t *group,       /* DEVICE [n_rows], or NULL: group 0 (n_groups == 1) */
+                     uint32_t flags,              /* KACC_WINDOW_ASSIGN_ALL                            */
+                     const kacc_slotmap *m,       /* the join's slot map, or NULL with term_count NULL */
+                     const uint32_t *term_slot,   /* DEVICE: the join's term_slot                      */
+                     const uint32_t *term_count,  /* DEVICE [m's nodes], or NULL: nothing retires      */
+                     void *stream);
+int kacc_window_mark(kacc_window *w, void *stream);
+int kacc_window_read(kacc_window *w,
+                     const kacc_top_rows *rows,   /* the kind's rows of the last interval batch     */
+                     const uint32_t *node_mask,   /* DEVICE [n_nodes], nonzero = listed; NULL = all */
+                     uint32_t *out_count,         /* DEVICE [n_groups]      or NULL */
+                     uint64_t *out_running,       /* DEVICE [n_groups * Z]  or NULL */
+                     uint64_t *out_retired,       /* DEVICE [n_groups * Z]  or NULL */
+                     uint32_t *out_retired_count, /* DEVICE [n_groups]      or NULL */
+                     uint64_t *out_total,         /* DEVICE [n_groups * Z]  or NULL */
+                     uint64_t *out_row,           /* DEVICE [n_rows * Z]    or NULL */
+                     void *stream);
+int kacc_window_download(kacc_window *w, uint64_t first, uint64_t count,
+                         uint64_t *host_base,     /* HOST [count * Z] or NULL */
+                         uint32_t *host_group);   /* HOST [count]     or NULL */
+
 /* Algorithmic HBM bytes of K consecutive intervals of these sizes: K times
  * kacc_interval_bytes, or (carried != 0: kacc_run_intervals' one-launch path,
  * which reads the engine state a node / row / aggregate needs once and carries

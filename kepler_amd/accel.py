@@ -63,6 +63,7 @@ KACC_QUANT_MAX_PHI = 8  # kacc_group_quantiles: largest n_phi
 KACC_QUANT_MAX_QUERIES = 65536  # largest n_groups * n_phi
 KACC_GROUP_TOP_MAX_ITEMS = 1 << 20  # kacc_group_top: largest n_groups * k
 KACC_TRACKER_READ_CLEAR = 0x1  # kacc_tracker_read: clear the listed nodes' trackers behind the read
+KACC_WINDOW_ASSIGN_ALL = 0x1  # kacc_window_step: every listed row stores its group id
 
 # kacc_table enum, in header order: (name, numpy dtype)
 TABLES = [
@@ -120,6 +121,12 @@ EXPORTS = [
     "kacc_group_hist",
     "kacc_group_quantiles",
     "kacc_group_top",
+    "kacc_window_create",
+    "kacc_window_destroy",
+    "kacc_window_step",
+    "kacc_window_mark",
+    "kacc_window_read",
+    "kacc_window_download",
     "kacc_zone_agg_create",
     "kacc_zone_agg_destroy",
     "kacc_zone_agg_read",
@@ -373,6 +380,14 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     if hasattr(lib, "kacc_group_top"):  # KACC_LIB A/B builds of earlier sources lack it
         lib.kacc_group_top.argtypes = ([c_void_p, c_int, c_uint32, c_uint32, POINTER(KaccTopRows), c_void_p, c_uint32]
                                        + [c_void_p] * 7)
+    if hasattr(lib, "kacc_window_create"):  # KACC_LIB A/B builds of earlier sources lack it
+        lib.kacc_window_create.argtypes = [c_void_p, c_int, c_uint32, POINTER(c_void_p)]
+        lib.kacc_window_destroy.argtypes = [c_void_p]
+        lib.kacc_window_destroy.restype = None
+        lib.kacc_window_step.argtypes = [c_void_p, POINTER(KaccTopRows), c_void_p, c_uint32] + [c_void_p] * 4
+        lib.kacc_window_mark.argtypes = [c_void_p, c_void_p]
+        lib.kacc_window_read.argtypes = [c_void_p, POINTER(KaccTopRows)] + [c_void_p] * 8
+        lib.kacc_window_download.argtypes = [c_void_p, c_uint64, c_uint64, c_void_p, c_void_p]
     lib.kacc_last_error_copy.argtypes = [c_void_p, c_char_p, ctypes.c_size_t]
     lib.kacc_last_error_copy.restype = ctypes.c_size_t
     lib.kacc_create_multi.argtypes = [POINTER(c_int), c_int, POINTER(KaccConfig), POINTER(c_void_p),
@@ -1001,6 +1016,70 @@ class Tracker:
     def close(self) -> None:
         if self.handle:
             self.lib.kacc_tracker_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Window:
+    """Energy over a window, summed by group, for one workload kind (kacc_window_*): per slot the
+    total at the window's start and the group of its workload, per group what the workloads that
+    terminated inside the window used in it."""
+
+    def __init__(self, accel: Accel, kind: int, n_groups: int):
+        self.accel = accel
+        self.lib = accel.lib
+        self.zones = accel.zones
+        self.n_groups = n_groups
+        self.slots = int((accel.cfg.proc_slots, accel.cfg.ctr_slots, accel.cfg.vm_slots, accel.cfg.pod_slots)[kind])
+        h = c_void_p()
+        accel._check(self.lib.kacc_window_create(accel.ctx, kind, n_groups, ctypes.byref(h)))
+        self.handle = h
+
+    def step(self, rows: KaccTopRows, group_ptr: int = 0, flags: int = 0, slotmap: Optional["SlotMap"] = None,
+             term_slot_ptr: int = 0, term_count_ptr: int = 0, stream: int = 0) -> None:
+        """kacc_window_step, once per interval after the slot join and before the interval: retires
+        the join's terminated slots (term_count_ptr 0: none), then adopts the listed NEW rows (every
+        listed row with KACC_WINDOW_ASSIGN_ALL) with the group id of each row (device u32 [n_rows];
+        0 = group 0, n_groups 1)."""
+        self.accel._check(self.lib.kacc_window_step(self.handle, ctypes.byref(rows), c_void_p(group_ptr or None), flags,
+                                                    slotmap.handle if slotmap is not None else None,
+                                                    c_void_p(term_slot_ptr or None), c_void_p(term_count_ptr or None),
+                                                    c_void_p(stream or None)))
+
+    def mark(self, stream: int = 0) -> None:
+        """kacc_window_mark: the window starts here (base = the totals, nothing retired; the groups stay)."""
+        self.accel._check(self.lib.kacc_window_mark(self.handle, c_void_p(stream or None)))
+
+    def read(self, rows: KaccTopRows, node_mask_ptr: int = 0, out_count_ptr: int = 0, out_running_ptr: int = 0,
+             out_retired_ptr: int = 0, out_retired_count_ptr: int = 0, out_total_ptr: int = 0, out_row_ptr: int = 0,
+             stream: int = 0) -> None:
+        """kacc_window_read: count and retired_count u32 [n_groups]; running, retired and total u64 µJ
+        [n_groups * Z]; row u64 µJ [n_rows * Z], every row's own increase (device pointers, each
+        optional).  The mask applies to the running part only."""
+        self.accel._check(self.lib.kacc_window_read(self.handle, ctypes.byref(rows), c_void_p(node_mask_ptr or None),
+                                                    c_void_p(out_count_ptr or None), c_void_p(out_running_ptr or None),
+                                                    c_void_p(out_retired_ptr or None),
+                                                    c_void_p(out_retired_count_ptr or None),
+                                                    c_void_p(out_total_ptr or None), c_void_p(out_row_ptr or None),
+                                                    c_void_p(stream or None)))
+
+    def download(self, first: int = 0, count: Optional[int] = None):
+        """(base u64 [count, Z], slot_group u32 [count]) of `count` slots from `first`: synchronous."""
+        if count is None:
+            count = self.slots - first
+        base = np.zeros((count, self.zones), dtype=np.uint64)
+        group = np.zeros(count, dtype=np.uint32)
+        self.accel._check(self.lib.kacc_window_download(self.handle, first, count, base.ctypes.data, group.ctypes.data))
+        return base, group
+
+    def close(self) -> None:
+        if self.handle:
+            self.lib.kacc_window_destroy(self.handle)
             self.handle = None
 
     def __del__(self):  # pragma: no cover
