@@ -139,3 +139,74 @@ def test_read_error_bit_set_and_cleared_every_read():
         np.testing.assert_array_equal(gs, want, err_msg=f"read {it}")
         good = np.repeat(os_ == 0, Z)
         np.testing.assert_array_equal(ge[good], oe[good], err_msg=f"read {it}")
+
+
+@pytest.mark.parametrize("N", [255, 256, 257])
+def test_read_error_at_socket_s_moves_only_the_sockets_before_it(N):
+    """Read 2 fails at socket n % 4 of zone n % 2 of every node n (one thread per node, 256 per
+    block: N sits on the block edge).  energy_zone.go:104-108 returns at once: the sockets before
+    the failed one have moved their last reading, the failed one and those after it have not — read
+    3's value of the failed zone says which, against the oracle and against the sum worked out here
+    (no wraps: the counters stay far below MaxEnergy)."""
+    Z, S = 2, 4
+    sub_max = np.full(N * Z * S, 1 << 40, dtype=np.uint64)
+    acc = accel.Accel(Z, nodes=N, proc_slots=1, ctr_slots=1, vm_slots=1, pod_slots=1)
+    g, o = GpuAgg(acc, N, S, sub_max), OracleZoneAgg(N, Z, S, sub_max)
+    k = np.arange(N * Z * S, dtype=np.uint64)
+    r1 = np.uint64(1000) + k * np.uint64(3)
+    r2 = r1 + np.uint64(100) + k % np.uint64(7)
+    r3 = r2 + np.uint64(10000) + k % np.uint64(11) * np.uint64(16)
+    node = np.arange(N)
+    st = np.zeros((N, Z, S), np.uint32)
+    st[node, node % 2, node % 4] = 1
+    failed = st.any(axis=2).reshape(-1)
+    assert failed.sum() == N
+    hand = r1.reshape(N * Z, S).sum(axis=1)  # a first reading adds the raw value
+    for it, (r, status) in enumerate([(r1, None), (r2, st.reshape(-1)), (r3, np.zeros(N * Z * S, np.uint32))]):
+        ge, gm, gs = g.read(r, status)
+        oe, om, os_ = o.read(r, status)
+        if it == 1:  # a failed zone's aggregate does not move
+            hand = hand + np.where(failed, 0, (r2 - r1).reshape(N * Z, S).sum(axis=1)).astype(np.uint64)
+        if it == 2:  # sockets before the failed one: since read 2; it and the later ones: since read 1
+            at = np.where(failed, st.reshape(N * Z, S).argmax(axis=1), S)
+            before = np.arange(S)[None, :] < at[:, None]
+            hand = hand + np.where(before, (r3 - r2).reshape(N * Z, S), (r3 - r1).reshape(N * Z, S)).sum(axis=1)
+        np.testing.assert_array_equal(gm, om)
+        np.testing.assert_array_equal(gs, os_, err_msg=f"read {it + 1}")
+        np.testing.assert_array_equal(gs, np.full(N, 1 if it == 1 else 0, np.uint32))
+        clean = ~failed if it == 1 else np.ones(N * Z, bool)
+        np.testing.assert_array_equal(ge[clean], oe[clean], err_msg=f"read {it + 1}")
+        np.testing.assert_array_equal(ge[clean], hand[clean], err_msg=f"read {it + 1} by hand")
+    g.z.close()
+    acc.close()
+
+
+def test_first_read_fails_then_earlier_socket_adds_a_delta_later_ones_their_raw_reading():
+    """A zone whose very first read fails at socket 1: socket 0 was seen (its last reading moved),
+    sockets 1.. were not, so the next clean read adds socket 0's delta and the raw readings of the
+    others (energy_zone.go:115-131)."""
+    N, Z, S = 3, 2, 3
+    sub_max = np.full(N * Z * S, 1 << 40, dtype=np.uint64)
+    acc = accel.Accel(Z, nodes=N, proc_slots=1, ctr_slots=1, vm_slots=1, pod_slots=1)
+    g, o = GpuAgg(acc, N, S, sub_max), OracleZoneAgg(N, Z, S, sub_max)
+    r1 = (np.arange(N * Z * S, dtype=np.uint64) + np.uint64(1)) * np.uint64(1000)
+    r2 = r1 + np.arange(N * Z * S, dtype=np.uint64) * np.uint64(7) + np.uint64(50)
+    st = np.zeros((N * Z, S), np.uint32)
+    zone = 1 * Z + 1  # node 1, zone 1
+    st[zone, 1] = 1
+    ge, _, gs = g.read(r1, st.reshape(-1))
+    oe, _, os_ = o.read(r1, st.reshape(-1))
+    np.testing.assert_array_equal(gs, os_)
+    assert gs.tolist() == [0, 1, 0]
+    ok = np.arange(N * Z) != zone
+    np.testing.assert_array_equal(ge[ok], oe[ok])
+    ge, _, gs = g.read(r2, np.zeros(N * Z * S, np.uint32))
+    oe, _, os_ = o.read(r2, np.zeros(N * Z * S, np.uint32))
+    np.testing.assert_array_equal(gs, os_)
+    assert gs.tolist() == [0, 0, 0]
+    np.testing.assert_array_equal(ge, oe)
+    a, b = r1.reshape(N * Z, S), r2.reshape(N * Z, S)
+    assert int(ge[zone]) == int(b[zone, 0] - a[zone, 0]) + int(b[zone, 1]) + int(b[zone, 2])
+    assert int(ge[zone - 1]) == int(b[zone - 1].sum())  # a zone read twice: first readings plus deltas
+    g.z.close()
+    acc.close()
