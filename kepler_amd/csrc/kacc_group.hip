@@ -28,8 +28,6 @@
 // faults.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
 #include "kacc_derive.hpp"
 #include "kacc_internal.hpp"
 #include "kacc_rows.hpp"
@@ -44,13 +42,15 @@ constexpr uint32_t kTile = kThreads * kPer;       // rows per tile
 constexpr uint32_t kSmallWords = 4096;            // u64 of LDS bins: 32 KiB, three workgroups per CU
 constexpr uint32_t kBigWords = 9984;              // 78 KiB, two workgroups per CU: 1,109 groups at Z = 4
 constexpr uint32_t kPassWords = 9728;             // a pass's bins: 76 KiB, 1,080 groups at Z = 4
+static_assert(kSmallWords == plan::kGroupLds.small_words && kBigWords == plan::kGroupLds.big_words &&
+                  kPassWords == plan::kGroupLds.pass_words, "the host plans with the kernels' LDS sizes");
 constexpr uint32_t kPassTile = kThreads * rows::kPassPer;  // the queues: 2 KiB per workgroup
 constexpr uint32_t kErrGroup = 1u << 13;          // a group id or a slot past its range, a row range
                                                   // outside the batch
 // the row word of the `rows` pass: the group id, the node's guard bits above it
 constexpr uint32_t kWordGroup = 0xffffu, kWordGuardShift = 16;
 static_assert(KACC_GROUP_MAX <= kWordGroup + 1u && KACC_MAX_ZONES <= 8u, "a row word holds the id and the guard bits");
-using rows::derived_bits, rows::kCus, rows::kMaxCopies, rows::kQueue, rows::lds_add;
+using rows::derived_bits, rows::kQueue, rows::lds_add;
 using u64x2 = __attribute__((ext_vector_type(2))) unsigned long long;
 
 struct Args {
@@ -304,15 +304,14 @@ int kacc_group_sums(kacc_ctx *ctx, kacc_kind kind, const kacc_top_rows *rows, co
   int rc = kacc::rows::resolve_kind(ctx, fn, kind);
   if (rc != KACC_OK) return rc;
   if (!rows) return kacc_fail(ctx, KACC_EINVAL, "%s: NULL argument", fn);
-  if (n_groups < 1 || n_groups > KACC_GROUP_MAX)
-    return kacc_fail(ctx, KACC_EINVAL, "%s: n_groups %u outside 1 .. %u", fn, n_groups, KACC_GROUP_MAX);
+  if ((rc = kacc::rows::check_groups(ctx, fn, n_groups)) != KACC_OK) return rc;
   if ((rc = kacc::rows::resolve(ctx, fn, kind, rows, node_mask, &a.v)) != KACC_OK) return rc;
   if (rows->n_rows && !group) return kacc_fail(ctx, KACC_EINVAL, "%s: NULL row array", fn);
   if (!out_count && !out_energy && !out_power_fx && !out_power && !out_dropped)
     return kacc_fail(ctx, KACC_EINVAL, "%s: no output array", fn);
-  KACC_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-  kacc::TimingScope timing(ctx);
+  kacc::rows::Call call(ctx, fn);
+  if ((rc = call.open(stream)) != KACC_OK) return rc;
+  hipStream_t st = call.st;
 
   const uint32_t Z = a.v.Z, W = 1u + 2u * Z;
   a.tiles = a.v.n_nodes ? kacc::rows::tiles_of(a.v.n_rows, kTile) : 0u;  // without a node no row is listed
@@ -325,72 +324,42 @@ int kacc_group_sums(kacc_ctx *ctx, kacc_kind kind, const kacc_top_rows *rows, co
   a.out_p = out_power;
   a.err = ctx->d_err;
 
-  // the grid: replicated bins while they fit the small LDS size, else one copy in the large
-  // one, else passes over group ranges
-  const uint32_t stride = (n_groups * W) | 1u;  // odd: the copies of a bin fall into different banks
-  uint32_t lds = kBigWords;
-  a.copies = 1;
-  a.copy_stride = n_groups * W;
-  a.passes = 1;
-  a.bins = n_groups;
-  if (stride <= kSmallWords) {
-    lds = kSmallWords;
-    a.copy_stride = stride;
-    while (a.copies < kMaxCopies && 2 * a.copies * stride <= kSmallWords) a.copies *= 2;
-  } else if (n_groups * W > kBigWords) {
-    a.bins = kPassWords / W;
-    a.passes = (n_groups + a.bins - 1) / a.bins;
-    a.copy_stride = 0;
-  }
-  const uint32_t wgs = kCus * (lds == kSmallWords ? 3u : 2u);
-  const uint32_t pass_tiles = kacc::rows::tiles_of(a.v.n_rows, kPassTile);
-  a.splits = std::max(1u, a.passes > 1 ? std::min(pass_tiles, wgs / a.passes) : std::min(a.tiles, wgs));
+  // the grid: replicated bins (an odd stride: the copies of a bin fall into different banks) while
+  // they fit the small LDS size, else one copy in the large one, else passes over group ranges
+  const kacc::plan::Bins b = kacc::plan::group_bins(n_groups, Z);
+  const bool small = b.regime == kacc::plan::kSmall;
+  a.copies = b.copies;
+  a.copy_stride = small ? (n_groups * W) | 1u : b.passes > 1 ? 0u : n_groups * W;
+  a.passes = b.passes;
+  a.bins = b.bins;
+  a.splits = kacc::plan::plan_splits(b, a.tiles, kacc::rows::tiles_of(a.v.n_rows, kPassTile));
 
   // temporaries, stream ordered: the accumulator, the node flags and, for passes, the row words
   // and nodes
-  const uint64_t acc_words = static_cast<uint64_t>(n_groups) * W;
   const uint64_t row_words = a.passes > 1 && a.tiles ? a.v.n_rows : 0;
-  uint64_t *tmp = nullptr;
-  KACC_HIP(ctx, hipMallocAsync(reinterpret_cast<void **>(&tmp), 8 * acc_words + 4ull * a.v.n_nodes + 8 * row_words, st));
-  a.acc = tmp;
-  a.v.nflags = reinterpret_cast<uint32_t *>(tmp + acc_words);
-  a.row_word = a.v.nflags + a.v.n_nodes;
-  a.row_node = a.row_word + row_words;
-  if (hipMemsetAsync(a.acc, 0, 8 * acc_words, st) != hipSuccess) rc = kacc_fail(ctx, KACC_EHIP, "%s: memset", fn);
+  kacc::plan::Layout tmp;
+  tmp.add(&a.acc, static_cast<uint64_t>(n_groups) * W, true);
+  tmp.add(&a.v.nflags, a.v.n_nodes);
+  for (uint32_t **p : {&a.row_word, &a.row_node}) tmp.add(p, row_words);
+  if ((rc = call.alloc(tmp)) != KACC_OK) return rc;
 
-  if (rc == KACC_OK) {
-    (void)hipGetLastError();  // clear a stale error of an earlier call
-    const dim3 block(kThreads);
-    if (a.v.n_nodes)
-      KACC_LAUNCH(kacc::rows::node_prep_kernel<kThreads>, dim3((a.v.n_nodes + kThreads - 1) / kThreads), block, 0, st, a.v,
-                  a.err, kErrGroup, static_cast<uint64_t *>(nullptr));
-    if (a.tiles) {
-      const bool z4 = Z == 4;
+  const dim3 block(kThreads);
+  if (a.v.n_nodes) kacc::rows::launch_node_prep<kThreads>(a.v, a.err, kErrGroup, nullptr, st);
+  if (a.tiles) {
+    kacc::rows::dispatch_zones(Z, [&](auto z) {
       if (a.passes > 1) {
         KACC_LAUNCH(rows_kernel, dim3(a.tiles), block, 0, st, a);
-        const dim3 grid(a.passes * a.splits);
-        if (z4)
-          KACC_LAUNCH(pass_kernel<4>, grid, block, 0, st, a);
-        else
-          KACC_LAUNCH(pass_kernel<0>, grid, block, 0, st, a);
-      } else if (lds == kSmallWords) {
-        if (z4)
-          KACC_LAUNCH((bin_kernel<4, kSmallWords>), dim3(a.splits), block, 0, st, a);
-        else
-          KACC_LAUNCH((bin_kernel<0, kSmallWords>), dim3(a.splits), block, 0, st, a);
+        KACC_LAUNCH(pass_kernel<z()>, dim3(a.passes * a.splits), block, 0, st, a);
+      } else if (small) {
+        KACC_LAUNCH((bin_kernel<z(), kSmallWords>), dim3(a.splits), block, 0, st, a);
       } else {
-        if (z4)
-          KACC_LAUNCH((bin_kernel<4, kBigWords>), dim3(a.splits), block, 0, st, a);
-        else
-          KACC_LAUNCH((bin_kernel<0, kBigWords>), dim3(a.splits), block, 0, st, a);
+        KACC_LAUNCH((bin_kernel<z(), kBigWords>), dim3(a.splits), block, 0, st, a);
       }
-    }
-    const uint64_t words = static_cast<uint64_t>(n_groups) * Z;
-    KACC_LAUNCH(finish_kernel, dim3(static_cast<uint32_t>((words + kThreads - 1) / kThreads)), block, 0, st, a);
-    if (hipGetLastError() != hipSuccess) rc = kacc_fail(ctx, KACC_EHIP, "%s: launch", fn);
+    });
   }
-  (void)hipFreeAsync(tmp, st);
-  return rc;
+  const uint64_t words = static_cast<uint64_t>(n_groups) * Z;
+  KACC_LAUNCH(finish_kernel, dim3(static_cast<uint32_t>((words + kThreads - 1) / kThreads)), block, 0, st, a);
+  return call.finish();
 }
 
 }  // extern "C"

@@ -40,7 +40,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 
 #include "kacc_derive.hpp"
 #include "kacc_internal.hpp"
@@ -63,7 +62,8 @@ constexpr uint32_t kSortThreads = 256;       // sort_out: four groups (k <= 64) 
 constexpr uint32_t kWaveK = 64;              // the largest k a wave sorts alone
 constexpr uint32_t kErrTop = 1u << 9;        // "top list": an id or a slot past its range, a row range outside the batch
 constexpr uint32_t kNone = 0xffffffffu;      // the group word of a row that is not ranked; the fill
-using rows::kCus, rows::kMaxCopies;
+static_assert(kDigits == plan::kDigits && kLdsWords == plan::kDigitWords, "the host plans with the kernels' LDS size");
+using rows::kCus, rows::knob;  // knob: the tuning knobs of tools/bench_gtop.py
 using rows::kDerived, rows::kEnergy, rows::kStored;  // the table of the values
 
 enum Mode { kFirstKey = 0, kKey = 1, kRow = 2 };  // what a digit pass counts
@@ -398,13 +398,6 @@ __global__ __launch_bounds__(kSortThreads) void sort_out_kernel(const Args a) {
   }
 }
 
-// A tuning knob of tools/bench_gtop.py: the value of an environment variable, at most `cap`.
-inline uint32_t knob(const char *name, uint32_t dflt, uint32_t cap) {
-  const char *s = std::getenv(name);
-  if (!s || !*s) return dflt;
-  return static_cast<uint32_t>(std::min<unsigned long>(std::strtoul(s, nullptr, 10), cap));
-}
-
 template <int kMode>
 void launch_digit(const Args &a, bool lds, uint32_t grid, uint32_t shift, hipStream_t st) {
   if (lds)
@@ -439,8 +432,7 @@ int kacc_group_top(kacc_ctx *ctx, kacc_table t, uint32_t zone, uint32_t k, const
   if (rc != KACC_OK) return rc;
   if (!rows) return kacc_fail(ctx, KACC_EINVAL, "%s: NULL argument", fn);
   if (k < 1 || k > KACC_TOP_MAX) return kacc_fail(ctx, KACC_EINVAL, "%s: k = %u outside 1 .. %u", fn, k, KACC_TOP_MAX);
-  if (n_groups < 1 || n_groups > KACC_GROUP_MAX)
-    return kacc_fail(ctx, KACC_EINVAL, "%s: n_groups %u outside 1 .. %u", fn, n_groups, KACC_GROUP_MAX);
+  if ((rc = kacc::rows::check_groups(ctx, fn, n_groups)) != KACC_OK) return rc;
   if (static_cast<uint64_t>(n_groups) * k > KACC_GROUP_TOP_MAX_ITEMS)
     return kacc_fail(ctx, KACC_EINVAL, "%s: %u groups x k = %u > %u", fn, n_groups, k, KACC_GROUP_TOP_MAX_ITEMS);
   if (!group && n_groups != 1) return kacc_fail(ctx, KACC_EINVAL, "%s: NULL group with n_groups %u", fn, n_groups);
@@ -448,11 +440,10 @@ int kacc_group_top(kacc_ctx *ctx, kacc_table t, uint32_t zone, uint32_t k, const
   if (!out_count && !out_row && !out_slot && !out_node && !out_value)
     return kacc_fail(ctx, KACC_EINVAL, "%s: no output array", fn);
 
-  KACC_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-  kacc::TimingScope timing(ctx);
+  kacc::rows::Call call(ctx, fn);
+  if ((rc = call.open(stream)) != KACC_OK) return rc;
+  hipStream_t st = call.st;
 
-  const int src = tab.src;
   const uint32_t G = n_groups;
   a.words = tab.words;
   a.zone = zone;
@@ -471,12 +462,8 @@ int kacc_group_top(kacc_ctx *ctx, kacc_table t, uint32_t zone, uint32_t k, const
   const bool lds = G <= knob("KACC_GTOP_LDS_GROUPS", kLdsGroups, kLdsGroups);
   a.merge_rounds = knob("KACC_GTOP_MERGE_ROUNDS", kMergeRounds, kMaxMergeRounds);
   a.row_exit = knob("KACC_GTOP_ROW_EXIT", 1u, 1u);
-  a.copies = 1;
-  a.stride = G * kDigits;
-  if (lds && 2u * (a.stride | 1u) <= kLdsWords) {
-    a.stride |= 1u;
-    while (a.copies < kMaxCopies && 2u * a.copies * a.stride <= kLdsWords) a.copies *= 2;
-  }
+  a.copies = kacc::plan::digit_copies(G, lds);
+  a.stride = G * kDigits | (a.copies > 1 ? 1u : 0u);
   // without a node no row is listed
   a.tiles = a.v.n_nodes ? kacc::rows::tiles_of(a.v.n_rows, kTile) : 0u;
   // persistent grids: two workgroups of 8 waves per CU with the LDS counters, four without
@@ -492,64 +479,41 @@ int kacc_group_top(kacc_ctx *ctx, kacc_table t, uint32_t zone, uint32_t k, const
   // temporaries, stream ordered: the counters and the groups' state (zeroed), the row records,
   // the segments, the node flags
   const uint64_t n_rows = a.tiles ? a.v.n_rows : 0, ents = static_cast<uint64_t>(G) * k;
-  const uint64_t zeroed = (4ull * G * kDigits + 8ull * G + 5ull * 4ull * G + 4ull + 7ull) & ~7ull;
-  char *tmp = nullptr;
-  KACC_HIP(ctx, hipMallocAsync(reinterpret_cast<void **>(&tmp), zeroed + 12 * n_rows + 12 * ents + 4ull * a.v.n_nodes, st));
-  a.bins = reinterpret_cast<uint32_t *>(tmp);
-  a.thr = reinterpret_cast<uint64_t *>(a.bins + static_cast<uint64_t>(G) * kDigits);
-  a.rem = reinterpret_cast<uint32_t *>(a.thr + G);
-  a.count = a.rem + G;
-  a.rthr = a.count + G;
-  a.cut = a.rthr + G;
-  a.cursor = a.cut + G;
-  a.any_cut = a.cursor + G;
-  a.row_key = reinterpret_cast<uint64_t *>(tmp + zeroed);
-  a.seg_key = a.row_key + n_rows;
-  a.row_group = reinterpret_cast<uint32_t *>(a.seg_key + ents);
-  a.seg_row = a.row_group + n_rows;
-  a.v.nflags = a.seg_row + ents;
-  if (hipMemsetAsync(tmp, 0, zeroed, st) != hipSuccess) rc = kacc_fail(ctx, KACC_EHIP, "%s: memset", fn);
+  kacc::plan::Layout tmp;
+  tmp.add(&a.bins, static_cast<uint64_t>(G) * kDigits, true);
+  tmp.add(&a.thr, G, true);
+  for (uint32_t **p : {&a.rem, &a.count, &a.rthr, &a.cut, &a.cursor}) tmp.add(p, G, true);
+  tmp.add(&a.any_cut, 1, true);
+  tmp.add(&a.row_key, n_rows);
+  tmp.add(&a.seg_key, ents);
+  tmp.add(&a.row_group, n_rows);
+  tmp.add(&a.seg_row, ents);
+  tmp.add(&a.v.nflags, a.v.n_nodes);
+  if ((rc = call.alloc(tmp)) != KACC_OK) return rc;
 
-  if (rc == KACC_OK) {
-    (void)hipGetLastError();  // clear a stale error of an earlier call
-    const dim3 block(kThreads);
-    if (a.v.n_nodes)
-      KACC_LAUNCH(kacc::rows::node_prep_kernel<kThreads>, dim3((a.v.n_nodes + kThreads - 1) / kThreads), block, 0, st, a.v,
-                  a.err, kErrTop, static_cast<uint64_t *>(nullptr));
-    if (a.tiles) {  // else every group is empty: the zeroed state says so
-      if (src == kEnergy)
-        KACC_LAUNCH(keys_kernel<kEnergy>, dim3(a.tiles), block, 0, st, a);
-      else if (src == kStored)
-        KACC_LAUNCH(keys_kernel<kStored>, dim3(a.tiles), block, 0, st, a);
+  const dim3 block(kThreads);
+  if (a.v.n_nodes) kacc::rows::launch_node_prep<kThreads>(a.v, a.err, kErrTop, nullptr, st);
+  if (a.tiles) {  // else every group is empty: the zeroed state says so
+    kacc::rows::dispatch_src(tab.src, [&](auto s) { KACC_LAUNCH(keys_kernel<s()>, dim3(a.tiles), block, 0, st, a); });
+    const dim3 pick_grid((G + kPickThreads / 64u - 1) / (kPickThreads / 64u));
+    for (uint32_t pass = 0; pass < kKeyPasses; ++pass) {
+      const uint32_t shift = 8u * (kKeyPasses - 1u - pass);
+      if (pass == 0)
+        launch_digit<kFirstKey>(a, lds, grid, shift, st);
       else
-        KACC_LAUNCH(keys_kernel<kDerived>, dim3(a.tiles), block, 0, st, a);
-      const dim3 pick_grid((G + kPickThreads / 64u - 1) / (kPickThreads / 64u));
-      for (uint32_t pass = 0; pass < kKeyPasses; ++pass) {
-        const uint32_t shift = 8u * (kKeyPasses - 1u - pass);
-        if (pass == 0)
-          launch_digit<kFirstKey>(a, lds, grid, shift, st);
-        else
-          launch_digit<kKey>(a, lds, grid, shift, st);
-        const uint32_t what = pass == 0 ? kPickFirst : pass + 1 == kKeyPasses ? kPickLastKey : kPickKey;
-        KACC_LAUNCH(pick_kernel, pick_grid, dim3(kPickThreads), 0, st, a, shift, what);
-      }
-      for (uint32_t pass = 0; pass < row_passes; ++pass) {  // only a cut block of equal keys counts here
-        const uint32_t shift = 8u * (row_passes - 1u - pass);
-        launch_digit<kRow>(a, lds, grid, shift, st);
-        KACC_LAUNCH(pick_kernel, pick_grid, dim3(kPickThreads), 0, st, a, shift, static_cast<uint32_t>(kPickRow));
-      }
-      KACC_LAUNCH(emit_kernel, dim3(std::max(1u, std::min(a.tiles, kCus * 4u))), block, 0, st, a);
+        launch_digit<kKey>(a, lds, grid, shift, st);
+      const uint32_t what = pass == 0 ? kPickFirst : pass + 1 == kKeyPasses ? kPickLastKey : kPickKey;
+      KACC_LAUNCH(pick_kernel, pick_grid, dim3(kPickThreads), 0, st, a, shift, what);
     }
-    if (src == kEnergy)
-      launch_sort_out<kEnergy>(a, st);
-    else if (src == kStored)
-      launch_sort_out<kStored>(a, st);
-    else
-      launch_sort_out<kDerived>(a, st);
-    if (hipGetLastError() != hipSuccess) rc = kacc_fail(ctx, KACC_EHIP, "%s: launch", fn);
+    for (uint32_t pass = 0; pass < row_passes; ++pass) {  // only a cut block of equal keys counts here
+      const uint32_t shift = 8u * (row_passes - 1u - pass);
+      launch_digit<kRow>(a, lds, grid, shift, st);
+      KACC_LAUNCH(pick_kernel, pick_grid, dim3(kPickThreads), 0, st, a, shift, static_cast<uint32_t>(kPickRow));
+    }
+    KACC_LAUNCH(emit_kernel, dim3(std::max(1u, std::min(a.tiles, kCus * 4u))), block, 0, st, a);
   }
-  (void)hipFreeAsync(tmp, st);
-  return rc;
+  kacc::rows::dispatch_src(tab.src, [&](auto s) { launch_sort_out<s()>(a, st); });
+  return call.finish();
 }
 
 }  // extern "C"

@@ -38,8 +38,6 @@
 // pass's range), so no batch faults.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
 #include "kacc_derive.hpp"
 #include "kacc_internal.hpp"
 #include "kacc_rows.hpp"
@@ -56,6 +54,8 @@ constexpr uint32_t kTile = kThreads * kPer;       // rows per tile (kBigThreads 
 constexpr uint32_t kSmallWords = 8192;            // 32 KiB, three workgroups per CU: replicated counters
 constexpr uint32_t kBigWords = 20096;             // 78.5 KiB: 1,004 groups at 15 bounds
 constexpr uint32_t kPassWords = 19200;            // a pass's counters: 75 KiB, 960 groups at 15 bounds
+static_assert(kSmallWords == plan::kHistLds.small_words && kBigWords == plan::kHistLds.big_words &&
+                  kPassWords == plan::kHistLds.pass_words, "the host plans with the kernels' LDS sizes");
 constexpr uint32_t kPassTile = kThreads * rows::kPassPer;  // the queues: 4 KiB per workgroup
 constexpr uint32_t kErrHist = 1u << 14;           // a group id or a slot past its range, a row range
                                                   // outside the batch
@@ -65,7 +65,7 @@ constexpr uint32_t kWordGroup = 0xffffu, kWordIdxShift = 16, kWordIdx = 0x7fu;
 constexpr uint32_t kWordUnsummed = 1u << 23, kWordSum = 1u << 24, kWordNone = 0xffffffffu;
 static_assert(KACC_GROUP_MAX <= kWordGroup + 1u && KACC_HIST_MAX_BOUNDS + 2u <= kWordIdx,
               "a row word holds the group id and the counter index");
-using rows::kCus, rows::kMaxCopies, rows::kQueue, rows::lds_add;
+using rows::kQueue, rows::lds_add;
 using rows::kDerived, rows::kEnergy, rows::kStored;  // the table of the values
 
 struct Args {
@@ -289,8 +289,7 @@ int kacc_group_hist(kacc_ctx *ctx, kacc_table t, uint32_t zone, const kacc_top_r
   if (!rows || !bounds) return kacc_fail(ctx, KACC_EINVAL, "%s: NULL argument", fn);
   if (n_bounds < 1 || n_bounds > KACC_HIST_MAX_BOUNDS)
     return kacc_fail(ctx, KACC_EINVAL, "%s: n_bounds %u outside 1 .. %u", fn, n_bounds, KACC_HIST_MAX_BOUNDS);
-  if (n_groups < 1 || n_groups > KACC_GROUP_MAX)
-    return kacc_fail(ctx, KACC_EINVAL, "%s: n_groups %u outside 1 .. %u", fn, n_groups, KACC_GROUP_MAX);
+  if ((rc = kacc::rows::check_groups(ctx, fn, n_groups)) != KACC_OK) return rc;
   if (static_cast<uint64_t>(n_groups) * (n_bounds + 1u) > KACC_HIST_MAX_BINS)
     return kacc_fail(ctx, KACC_EINVAL, "%s: %u groups x %u bins > %u", fn, n_groups, n_bounds + 1u, KACC_HIST_MAX_BINS);
   if (!group && n_groups != 1) return kacc_fail(ctx, KACC_EINVAL, "%s: NULL group with n_groups %u", fn, n_groups);
@@ -305,11 +304,10 @@ int kacc_group_hist(kacc_ctx *ctx, kacc_table t, uint32_t zone, const kacc_top_r
     if (i && a.key[i] <= a.key[i - 1])
       return kacc_fail(ctx, KACC_EINVAL, "%s: the keys of bounds %u and %u are not strictly ascending", fn, i - 1, i);
   }
-  KACC_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-  kacc::TimingScope timing(ctx);
+  kacc::rows::Call call(ctx, fn);
+  if ((rc = call.open(stream)) != KACC_OK) return rc;
+  hipStream_t st = call.st;
 
-  const int src = tab.src;
   a.words = tab.words;
   a.zone = zone;
   a.n_bounds = n_bounds;
@@ -325,81 +323,45 @@ int kacc_group_hist(kacc_ctx *ctx, kacc_table t, uint32_t zone, const kacc_top_r
   // the grid: replicated counters while a copy (odd strides: the copies of a counter fall into
   // different banks) fits the small LDS size, else one copy in the large one, else passes over
   // group ranges
-  const uint32_t C = n_bounds + 3u, W = C + 2u;  // u32 words per group: the counters, the u64 sum
-  const uint32_t cnt_odd = (n_groups * C) | 1u, sum_odd = n_groups | 1u, per = cnt_odd + 2u * sum_odd;
-  uint32_t lds = kBigWords;
-  a.copies = 1;
-  a.cnt_stride = n_groups * C;
-  a.sum_stride = n_groups;
-  a.passes = 1;
-  a.bins = n_groups;
-  if (per <= kSmallWords) {
-    lds = kSmallWords;
-    a.cnt_stride = cnt_odd;
-    a.sum_stride = sum_odd;
-    while (a.copies < kMaxCopies && 2 * a.copies * per <= kSmallWords) a.copies *= 2;
-  } else if (n_groups * W > kBigWords) {
-    a.bins = kPassWords / W;
-    a.passes = (n_groups + a.bins - 1) / a.bins;
-  }
   // workgroups per CU: three of 512 threads at the small size, one of 1,024 at the large one, two of 512 in a pass
-  const bool big = a.passes == 1 && lds == kBigWords;
-  const uint32_t wgs = kCus * (lds == kSmallWords ? 3u : big ? 1u : 2u);
-  const uint32_t tile_rows = big ? kBigThreads * kPer : kTile;
+  const uint32_t C = n_bounds + 3u;  // a group's counters; with the u64 sum C + 2 u32 words
+  const kacc::plan::Bins b = kacc::plan::hist_bins(n_groups, n_bounds);
+  const bool small = b.regime == kacc::plan::kSmall, big = b.regime == kacc::plan::kBig;
+  a.copies = b.copies;
+  a.cnt_stride = small ? (n_groups * C) | 1u : n_groups * C;
+  a.sum_stride = small ? n_groups | 1u : n_groups;
+  a.passes = b.passes;
+  a.bins = b.bins;
   // without a node no row is listed
-  a.tiles = a.v.n_nodes ? kacc::rows::tiles_of(a.v.n_rows, tile_rows) : 0u;
-  const uint32_t pass_tiles = kacc::rows::tiles_of(a.v.n_rows, kPassTile);
-  a.splits = std::max(1u, a.passes > 1 ? std::min(pass_tiles, wgs / a.passes) : std::min(a.tiles, wgs));
+  a.tiles = a.v.n_nodes ? kacc::rows::tiles_of(a.v.n_rows, big ? kBigThreads * kPer : kTile) : 0u;
+  a.splits = kacc::plan::plan_splits(b, a.tiles, kacc::rows::tiles_of(a.v.n_rows, kPassTile));
 
   // temporaries, stream ordered: the accumulator, for passes the sum and row words, the node flags
-  const uint64_t acc_words = static_cast<uint64_t>(n_groups) * (C + 1u);
   const uint64_t row_words = a.passes > 1 && a.tiles ? a.v.n_rows : 0;
-  uint64_t *tmp = nullptr;
-  KACC_HIP(ctx, hipMallocAsync(reinterpret_cast<void **>(&tmp), 8 * acc_words + 12 * row_words + 4ull * a.v.n_nodes, st));
-  a.acc = tmp;
-  a.row_fx = tmp + acc_words;
-  a.row_word = reinterpret_cast<uint32_t *>(a.row_fx + row_words);
-  a.v.nflags = a.row_word + row_words;
-  if (hipMemsetAsync(a.acc, 0, 8 * acc_words, st) != hipSuccess) rc = kacc_fail(ctx, KACC_EHIP, "%s: memset", fn);
+  kacc::plan::Layout tmp;
+  tmp.add(&a.acc, static_cast<uint64_t>(n_groups) * (C + 1u), true);
+  tmp.add(&a.row_fx, row_words);
+  tmp.add(&a.row_word, row_words);
+  tmp.add(&a.v.nflags, a.v.n_nodes);
+  if ((rc = call.alloc(tmp)) != KACC_OK) return rc;
 
-  if (rc == KACC_OK) {
-    (void)hipGetLastError();  // clear a stale error of an earlier call
-    const dim3 block(kThreads);
-    if (a.v.n_nodes)
-      KACC_LAUNCH(kacc::rows::node_prep_kernel<kThreads>, dim3((a.v.n_nodes + kThreads - 1) / kThreads), block, 0, st, a.v,
-                  a.err, kErrHist, static_cast<uint64_t *>(nullptr));
-    if (a.tiles) {
+  const dim3 block(kThreads);
+  if (a.v.n_nodes) kacc::rows::launch_node_prep<kThreads>(a.v, a.err, kErrHist, nullptr, st);
+  if (a.tiles) {
+    kacc::rows::dispatch_src(tab.src, [&](auto s) {
       if (a.passes > 1) {
-        if (src == kEnergy)
-          KACC_LAUNCH(rows_kernel<kEnergy>, dim3(a.tiles), block, 0, st, a);
-        else if (src == kStored)
-          KACC_LAUNCH(rows_kernel<kStored>, dim3(a.tiles), block, 0, st, a);
-        else
-          KACC_LAUNCH(rows_kernel<kDerived>, dim3(a.tiles), block, 0, st, a);
+        KACC_LAUNCH(rows_kernel<s()>, dim3(a.tiles), block, 0, st, a);
         KACC_LAUNCH(pass_kernel, dim3(a.passes * a.splits), block, 0, st, a);
-      } else if (lds == kSmallWords) {
-        if (src == kEnergy)
-          KACC_LAUNCH((bin_kernel<kEnergy, kSmallWords>), dim3(a.splits), block, 0, st, a);
-        else if (src == kStored)
-          KACC_LAUNCH((bin_kernel<kStored, kSmallWords>), dim3(a.splits), block, 0, st, a);
-        else
-          KACC_LAUNCH((bin_kernel<kDerived, kSmallWords>), dim3(a.splits), block, 0, st, a);
+      } else if (small) {
+        KACC_LAUNCH((bin_kernel<s(), kSmallWords>), dim3(a.splits), block, 0, st, a);
       } else {
-        const dim3 big_block(kBigThreads);
-        if (src == kEnergy)
-          KACC_LAUNCH((bin_kernel<kEnergy, kBigWords>), dim3(a.splits), big_block, 0, st, a);
-        else if (src == kStored)
-          KACC_LAUNCH((bin_kernel<kStored, kBigWords>), dim3(a.splits), big_block, 0, st, a);
-        else
-          KACC_LAUNCH((bin_kernel<kDerived, kBigWords>), dim3(a.splits), big_block, 0, st, a);
+        KACC_LAUNCH((bin_kernel<s(), kBigWords>), dim3(a.splits), dim3(kBigThreads), 0, st, a);
       }
-    }
-    const uint64_t words = static_cast<uint64_t>(n_groups) * (n_bounds + 1u);
-    KACC_LAUNCH(finish_kernel, dim3(static_cast<uint32_t>((words + kThreads - 1) / kThreads)), block, 0, st, a);
-    if (hipGetLastError() != hipSuccess) rc = kacc_fail(ctx, KACC_EHIP, "%s: launch", fn);
+    });
   }
-  (void)hipFreeAsync(tmp, st);
-  return rc;
+  const uint64_t words = static_cast<uint64_t>(n_groups) * (n_bounds + 1u);
+  KACC_LAUNCH(finish_kernel, dim3(static_cast<uint32_t>((words + kThreads - 1) / kThreads)), block, 0, st, a);
+  return call.finish();
 }
 
 }  // extern "C"

@@ -105,6 +105,20 @@ class TimingScope {
   LaunchTiming t_;
   bool on_ = false;
 };
+
+// A valid workload kind's slot capacity and the index of its energy table.
+inline uint64_t kind_cap(const kacc_ctx *ctx, int kind) {
+  return kind == KACC_KIND_PROC ? ctx->cfg.proc_slots
+         : kind == KACC_KIND_CTR ? ctx->cfg.ctr_slots
+         : kind == KACC_KIND_VM ? ctx->cfg.vm_slots
+                                : ctx->cfg.pod_slots;
+}
+inline int kind_energy_table(int kind) {
+  return kind == KACC_KIND_PROC ? KACC_T_PROC_ENERGY
+         : kind == KACC_KIND_CTR ? KACC_T_CTR_ENERGY
+         : kind == KACC_KIND_VM ? KACC_T_VM_ENERGY
+                                : KACC_T_POD_ENERGY;
+}
 }  // namespace kacc
 
 #define KACC_LAUNCH(kernel, grid, block, shmem, stream, ...)                                             \

@@ -339,14 +339,8 @@ int kacc_unpack(kacc_ctx *ctx, kacc_kind kind, uint32_t n, const uint32_t *slot_
   if (kind < KACC_KIND_PROC || kind > KACC_KIND_POD) return kacc_fail(ctx, KACC_EINVAL, "bad kind");
   KACC_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-  const int te = kind == KACC_KIND_PROC ? KACC_T_PROC_ENERGY
-                 : kind == KACC_KIND_CTR ? KACC_T_CTR_ENERGY
-                 : kind == KACC_KIND_VM ? KACC_T_VM_ENERGY
-                                        : KACC_T_POD_ENERGY;
-  const uint64_t cap = kind == KACC_KIND_PROC ? ctx->cfg.proc_slots
-                       : kind == KACC_KIND_CTR ? ctx->cfg.ctr_slots
-                       : kind == KACC_KIND_VM ? ctx->cfg.vm_slots
-                                              : ctx->cfg.pod_slots;
+  const int te = kacc::kind_energy_table(kind);
+  const uint64_t cap = kacc::kind_cap(ctx, kind);
   const uint64_t *e = static_cast<const uint64_t *>(ctx->tables[te]);
   // processes, containers, VMs: power derived (kacc_derive.hpp); pods: the table
   const double *p = kind == KACC_KIND_POD ? static_cast<const double *>(ctx->tables[te + 1]) : nullptr;

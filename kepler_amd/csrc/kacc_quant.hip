@@ -40,7 +40,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 
 #include "kacc_derive.hpp"
 #include "kacc_internal.hpp"
@@ -63,7 +62,8 @@ constexpr uint32_t kErrQuant = 1u << 15;     // a group id or a slot past its ra
 constexpr uint32_t kNone = 0xffffffffu;      // the group word of a row that is not ranked
 constexpr uint64_t kEmptyNan = 0x7ff8000000000001ull;    // out_value of a group without ranked rows
 constexpr uint64_t kInvalidNan = 0xfff8000000000000ull;  // out_value of Inf * 0 and Inf - Inf (header)
-using rows::kCus, rows::kMaxCopies;
+static_assert(kDigits == plan::kDigits && kLdsWords == plan::kDigitWords, "the host plans with the kernels' LDS size");
+using rows::kCus, rows::knob;  // knob: the tuning knobs of tools/bench_quant.py
 using rows::kDerived, rows::kEnergy, rows::kStored;  // the table of the values
 
 struct Args {
@@ -330,13 +330,6 @@ __global__ __launch_bounds__(kThreads) void finish_kernel(const Args a) {
   if (a.out_value) a.out_value[i] = __longlong_as_double(static_cast<long long>(value));
 }
 
-// A tuning knob of tools/bench_quant.py: the value of an environment variable, at most `cap`.
-inline uint32_t knob(const char *name, uint32_t dflt, uint32_t cap) {
-  const char *s = std::getenv(name);
-  if (!s || !*s) return dflt;
-  return static_cast<uint32_t>(std::min<unsigned long>(std::strtoul(s, nullptr, 10), cap));
-}
-
 }  // namespace quant
 }  // namespace kacc
 
@@ -356,8 +349,7 @@ int kacc_group_quantiles(kacc_ctx *ctx, kacc_table t, uint32_t zone, const kacc_
   if (!rows || !phi) return kacc_fail(ctx, KACC_EINVAL, "%s: NULL argument", fn);
   if (n_phi < 1 || n_phi > KACC_QUANT_MAX_PHI)
     return kacc_fail(ctx, KACC_EINVAL, "%s: n_phi %u outside 1 .. %u", fn, n_phi, KACC_QUANT_MAX_PHI);
-  if (n_groups < 1 || n_groups > KACC_GROUP_MAX)
-    return kacc_fail(ctx, KACC_EINVAL, "%s: n_groups %u outside 1 .. %u", fn, n_groups, KACC_GROUP_MAX);
+  if ((rc = kacc::rows::check_groups(ctx, fn, n_groups)) != KACC_OK) return rc;
   if (static_cast<uint64_t>(n_groups) * n_phi > KACC_QUANT_MAX_QUERIES)
     return kacc_fail(ctx, KACC_EINVAL, "%s: %u groups x %u quantiles > %u", fn, n_groups, n_phi, KACC_QUANT_MAX_QUERIES);
   if (!group && n_groups != 1) return kacc_fail(ctx, KACC_EINVAL, "%s: NULL group with n_groups %u", fn, n_groups);
@@ -369,11 +361,10 @@ int kacc_group_quantiles(kacc_ctx *ctx, kacc_table t, uint32_t zone, const kacc_
   if (!out_count && !out_nan && !out_lo && !out_hi && !out_weight && !out_value)
     return kacc_fail(ctx, KACC_EINVAL, "%s: no output array", fn);
 
-  KACC_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-  kacc::TimingScope timing(ctx);
+  kacc::rows::Call call(ctx, fn);
+  if ((rc = call.open(stream)) != KACC_OK) return rc;
+  hipStream_t st = call.st;
 
-  const int src = tab.src;
   const uint32_t Q = n_groups * n_phi;
   a.words = tab.words;
   a.zone = zone;
@@ -394,12 +385,8 @@ int kacc_group_quantiles(kacc_ctx *ctx, kacc_table t, uint32_t zone, const kacc_
   // of a counter fall into different banks, while they fit more than once), else in global memory
   const bool lds = Q <= knob("KACC_QUANT_LDS_QUERIES", kLdsQueries, kLdsQueries);
   a.merge_rounds = knob("KACC_QUANT_MERGE_ROUNDS", kMergeRounds, kMaxMergeRounds);
-  a.copies = 1;
-  a.stride = Q * kDigits;
-  if (lds && 2u * (a.stride | 1u) <= kLdsWords) {
-    a.stride |= 1u;
-    while (a.copies < kMaxCopies && 2u * a.copies * a.stride <= kLdsWords) a.copies *= 2;
-  }
+  a.copies = kacc::plan::digit_copies(Q, lds);
+  a.stride = Q * kDigits | (a.copies > 1 ? 1u : 0u);
   // without a node no row is listed
   a.tiles = a.v.n_nodes ? kacc::rows::tiles_of(a.v.n_rows, kTile) : 0u;
   // persistent grids: two workgroups of 8 waves per CU with the LDS counters, four without
@@ -407,54 +394,37 @@ int kacc_group_quantiles(kacc_ctx *ctx, kacc_table t, uint32_t zone, const kacc_
 
   // temporaries, stream ordered: the counters and the queries' state (zeroed), the row records, the node flags
   const uint64_t n_rows = a.tiles ? a.v.n_rows : 0;
-  const uint64_t zeroed = (4ull * Q * kDigits + 16ull * Q + 12ull * Q + 4ull * n_groups + 7ull) & ~7ull;
-  char *tmp = nullptr;
-  KACC_HIP(ctx, hipMallocAsync(reinterpret_cast<void **>(&tmp), zeroed + 12 * n_rows + 4ull * a.v.n_nodes, st));
-  a.bins = reinterpret_cast<uint32_t *>(tmp);
-  a.prefix = reinterpret_cast<uint64_t *>(a.bins + static_cast<uint64_t>(Q) * kDigits);
-  a.succ = a.prefix + Q;
-  a.rem = reinterpret_cast<uint32_t *>(a.succ + Q);
-  a.lower = a.rem + Q;
-  a.count = a.lower + Q;
-  a.nan = a.count + Q;
-  a.row_key = reinterpret_cast<uint64_t *>(tmp + zeroed);
-  a.row_group = reinterpret_cast<uint32_t *>(a.row_key + n_rows);
-  a.v.nflags = a.row_group + n_rows;
-  if (hipMemsetAsync(tmp, 0, zeroed, st) != hipSuccess) rc = kacc_fail(ctx, KACC_EHIP, "%s: memset", fn);
+  kacc::plan::Layout tmp;
+  tmp.add(&a.bins, static_cast<uint64_t>(Q) * kDigits, true);
+  for (uint64_t **p : {&a.prefix, &a.succ}) tmp.add(p, Q, true);
+  for (uint32_t **p : {&a.rem, &a.lower, &a.count}) tmp.add(p, Q, true);
+  tmp.add(&a.nan, n_groups, true);
+  tmp.add(&a.row_key, n_rows);
+  tmp.add(&a.row_group, n_rows);
+  tmp.add(&a.v.nflags, a.v.n_nodes);
+  if ((rc = call.alloc(tmp)) != KACC_OK) return rc;
 
-  if (rc == KACC_OK) {
-    (void)hipGetLastError();  // clear a stale error of an earlier call
-    const dim3 block(kThreads);
-    if (a.v.n_nodes)
-      KACC_LAUNCH(kacc::rows::node_prep_kernel<kThreads>, dim3((a.v.n_nodes + kThreads - 1) / kThreads), block, 0, st, a.v,
-                  a.err, kErrQuant, static_cast<uint64_t *>(nullptr));
-    if (a.tiles) {  // else every group is empty: the zeroed state says so
-      if (src == kEnergy)
-        KACC_LAUNCH(keys_kernel<kEnergy>, dim3(a.tiles), block, 0, st, a);
-      else if (src == kStored)
-        KACC_LAUNCH(keys_kernel<kStored>, dim3(a.tiles), block, 0, st, a);
+  const dim3 block(kThreads);
+  if (a.v.n_nodes) kacc::rows::launch_node_prep<kThreads>(a.v, a.err, kErrQuant, nullptr, st);
+  if (a.tiles) {  // else every group is empty: the zeroed state says so
+    kacc::rows::dispatch_src(tab.src, [&](auto s) { KACC_LAUNCH(keys_kernel<s()>, dim3(a.tiles), block, 0, st, a); });
+    const dim3 pick_grid((Q + kPickThreads / 64u - 1) / (kPickThreads / 64u));
+    for (uint32_t pass = 0; pass < kPasses; ++pass) {
+      const uint32_t shift = 8u * (kPasses - 1u - pass);
+      if (lds && pass == 0)
+        KACC_LAUNCH(digit_lds_kernel<true>, dim3(grid), block, 0, st, a, shift);
+      else if (lds)
+        KACC_LAUNCH(digit_lds_kernel<false>, dim3(grid), block, 0, st, a, shift);
+      else if (pass == 0)
+        KACC_LAUNCH(digit_global_kernel<true>, dim3(grid), block, 0, st, a, shift);
       else
-        KACC_LAUNCH(keys_kernel<kDerived>, dim3(a.tiles), block, 0, st, a);
-      const dim3 pick_grid((Q + kPickThreads / 64u - 1) / (kPickThreads / 64u));
-      for (uint32_t pass = 0; pass < kPasses; ++pass) {
-        const uint32_t shift = 8u * (kPasses - 1u - pass);
-        if (lds && pass == 0)
-          KACC_LAUNCH(digit_lds_kernel<true>, dim3(grid), block, 0, st, a, shift);
-        else if (lds)
-          KACC_LAUNCH(digit_lds_kernel<false>, dim3(grid), block, 0, st, a, shift);
-        else if (pass == 0)
-          KACC_LAUNCH(digit_global_kernel<true>, dim3(grid), block, 0, st, a, shift);
-        else
-          KACC_LAUNCH(digit_global_kernel<false>, dim3(grid), block, 0, st, a, shift);
-        KACC_LAUNCH(pick_kernel, pick_grid, dim3(kPickThreads), 0, st, a, shift, pass == 0 ? 1u : 0u);
-      }
-      KACC_LAUNCH(succ_kernel, dim3(grid), block, 0, st, a);
+        KACC_LAUNCH(digit_global_kernel<false>, dim3(grid), block, 0, st, a, shift);
+      KACC_LAUNCH(pick_kernel, pick_grid, dim3(kPickThreads), 0, st, a, shift, pass == 0 ? 1u : 0u);
     }
-    KACC_LAUNCH(finish_kernel, dim3((Q + kThreads - 1) / kThreads), block, 0, st, a);
-    if (hipGetLastError() != hipSuccess) rc = kacc_fail(ctx, KACC_EHIP, "%s: launch", fn);
+    KACC_LAUNCH(succ_kernel, dim3(grid), block, 0, st, a);
   }
-  (void)hipFreeAsync(tmp, st);
-  return rc;
+  KACC_LAUNCH(finish_kernel, dim3((Q + kThreads - 1) / kThreads), block, 0, st, a);
+  return call.finish();
 }
 
 }  // extern "C"

@@ -1,18 +1,25 @@
 // The rows of an interval batch for the workload row queries - kacc_top.hip, kacc_select.hip,
-// kacc_group.hip, kacc_hist.hip, kacc_quant.hip (device and host helpers, not part
-// of the public ABI).  All five read the rows of the caller's last interval batch (kacc_top_rows) for one
-// workload kind and ask the same things: is the row listed, is its slot valid, what is its
-// value (an energy word, a stored pod power, or the derived ratio[slot] · ActivePower[node]
-// under the node's guard) or its Z-word record.  Here, once: the value rules, the row view, the
-// per-node flag word and its kernel, the tile-to-node search, the tile prelude that locates a
-// lane's rows, the pass queue, and the host resolver of a call's kind and rows.
+// kacc_group.hip, kacc_hist.hip, kacc_quant.hip, kacc_gtop.hip, kacc_window.hip (DESIGN §4.10b;
+// device and host helpers, not part of the public ABI).  All seven read the rows of the caller's
+// last interval batch (kacc_top_rows) for one workload kind and ask the same things: is the row
+// listed, is its slot valid, what is its value (an energy word, a stored pod power, or the derived
+// ratio[slot] · ActivePower[node] under the node's guard) or its Z-word record.  Here, once: the
+// value rules, the row view, the per-node flag word and its kernel, the tile-to-node search, the
+// tile prelude that locates a lane's rows, the pass queue, the host resolver of a call's kind and
+// rows, and the host's call layer: the call scope with its scratch, the source and zone
+// dispatch and the small helpers (the scratch layout and the LDS plan are kacc_plan.hpp's).
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cstdlib>
+#include <optional>
+#include <type_traits>
+
 #include "kacc_derive.hpp"
 #include "kacc_internal.hpp"
+#include "kacc_plan.hpp"
 
 namespace kacc {
 namespace rows {
@@ -24,8 +31,7 @@ enum Src { kEnergy = 0, kStored = 1, kDerived = 2 };  // where a row's value com
 constexpr uint32_t kListed = 1u << 31;  // node flag word: bit z = zone z passed the guard
 static_assert(KACC_MAX_ZONES < 31, "the zones' guard bits and kListed share a word");
 constexpr uint64_t kFxLimit = (1023ull + 50ull) << 52;  // the bits of 2^50: |p| at or past it has no fx
-constexpr uint32_t kCus = 256;        // MI355X: the persistent grids of the group queries
-constexpr uint32_t kMaxCopies = 64;   // one copy of a group query's LDS bins per lane of a wave
+using plan::kCus, plan::kMaxCopies;   // the persistent grids and the LDS copies of the group queries
 constexpr uint32_t kQueue = 128;      // a wave's queued rows in a pass
 constexpr uint32_t kPassPer = 16;     // row words per lane and step of a pass
 
@@ -321,8 +327,6 @@ inline int resolve(kacc_ctx *ctx, const char *fn, int kind, const kacc_top_rows 
                      (unsigned long long)ctx->cfg.nodes);
   if (!rows->row_off || (rows->n_rows && !rows->slot)) return kacc_fail(ctx, KACC_EINVAL, "%s: NULL row array", fn);
   const bool pod = kind == KACC_KIND_POD;
-  const int te = pod ? KACC_T_POD_ENERGY : kind == KACC_KIND_PROC ? KACC_T_PROC_ENERGY
-                 : kind == KACC_KIND_CTR ? KACC_T_CTR_ENERGY : KACC_T_VM_ENERGY;
   *v = View{};
   v->n_nodes = rows->n_nodes;
   v->n_rows = rows->n_rows;
@@ -330,17 +334,99 @@ inline int resolve(kacc_ctx *ctx, const char *fn, int kind, const kacc_top_rows 
   v->slot = rows->slot;
   v->node_status = rows->node_status;
   v->node_mask = node_mask;
-  v->cap = kind == KACC_KIND_PROC ? ctx->cfg.proc_slots
-           : kind == KACC_KIND_CTR ? ctx->cfg.ctr_slots
-           : kind == KACC_KIND_VM ? ctx->cfg.vm_slots
-                                  : ctx->cfg.pod_slots;
+  v->cap = kind_cap(ctx, kind);
   v->Z = ctx->cfg.zones;
   v->tab_stride = pod ? 2 * v->Z : v->Z;
-  v->tab_e = static_cast<const uint64_t *>(ctx->tables[te]);
+  v->tab_e = static_cast<const uint64_t *>(ctx->tables[kind_energy_table(kind)]);
   v->tab_p = pod ? static_cast<const uint64_t *>(ctx->tables[KACC_T_POD_POWER]) : nullptr;  // Z words into the record
   v->pd = kacc_derive(ctx, static_cast<kacc_kind>(pod ? KACC_KIND_PROC : kind));
   v->derived = !pod;  // the kind's power, whichever table a call's values come from
   return KACC_OK;
+}
+// The group count's range, one rule for every call that takes one.
+inline int check_groups(kacc_ctx *ctx, const char *fn, uint32_t n_groups) {
+  if (n_groups < 1 || n_groups > KACC_GROUP_MAX)
+    return kacc_fail(ctx, KACC_EINVAL, "%s: n_groups %u outside 1 .. %u", fn, n_groups, KACC_GROUP_MAX);
+  return KACC_OK;
+}
+
+// ---- the host's call layer -----------------------------------------------------------------
+
+// One entry point's device work, after its argument checks: open() sets the device, resolves
+// the stream, takes the context's pending timing events and drops a stale launch error;
+// alloc() makes the call's one scratch allocation and its one memset; finish() turns a launch
+// error into the return code.  The scratch is freed, stream ordered, on every path out.
+class Call {
+ public:
+  kacc_ctx *const ctx;
+  const char *const fn;
+  hipStream_t st = nullptr;
+
+  Call(kacc_ctx *c, const char *f) : ctx(c), fn(f) {}
+  ~Call() {
+    if (tmp_) (void)hipFreeAsync(tmp_, st);
+  }
+
+  int open(void *stream) {
+    KACC_HIP(ctx, hipSetDevice(ctx->device));
+    st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    timing_.emplace(ctx);
+    (void)hipGetLastError();  // as everywhere in the library: finish() reports this call's launches alone
+    return KACC_OK;
+  }
+  // The layout's arrays (none: no allocation), at least min_bytes; its pointers are set.
+  int alloc(const plan::Layout &l, uint64_t min_bytes = 0) {
+    const uint64_t bytes = std::max(l.bytes(), min_bytes);
+    if (!bytes) return KACC_OK;
+    KACC_HIP(ctx, hipMallocAsync(&tmp_, bytes, st));
+    l.bind(tmp_);
+    if (l.zeroed() && hipMemsetAsync(tmp_, 0, l.zeroed(), st) != hipSuccess)
+      return kacc_fail(ctx, KACC_EHIP, "%s: memset", fn);
+    return KACC_OK;
+  }
+  int finish() {
+    return hipGetLastError() != hipSuccess ? kacc_fail(ctx, KACC_EHIP, "%s: launch", fn) : KACC_OK;
+  }
+
+ private:
+  std::optional<TimingScope> timing_;
+  void *tmp_ = nullptr;
+};
+
+// f(std::integral_constant<int, kSrc>{}) for the Src of a call's values: one generic lambda
+// around the launch of a kernel<kSrc>.
+template <class F>
+void dispatch_src(int src, F f) {
+  if (src == kEnergy)
+    f(std::integral_constant<int, kEnergy>{});
+  else if (src == kStored)
+    f(std::integral_constant<int, kStored>{});
+  else
+    f(std::integral_constant<int, kDerived>{});
+}
+// The same for a kernel<kZ>: 4 when that is the zone count (16-byte loads), else 0: any Z.
+template <class F>
+void dispatch_zones(uint32_t Z, F f) {
+  if (Z == 4)
+    f(std::integral_constant<uint32_t, 4>{});
+  else
+    f(std::integral_constant<uint32_t, 0>{});
+}
+
+// The launch of the view's node_prep_kernel: one thread per node, and one more when `zero`
+// (a scratch word to clear) makes it run without a node too.
+template <uint32_t kThreads>
+void launch_node_prep(const View &v, uint32_t *err, uint32_t err_bit, uint64_t *zero, hipStream_t st) {
+  const uint64_t threads = v.n_nodes + (zero ? 1ull : 0ull);
+  KACC_LAUNCH(node_prep_kernel<kThreads>, dim3(static_cast<uint32_t>((threads + kThreads - 1) / kThreads)),
+              dim3(kThreads), 0, st, v, err, err_bit, zero);
+}
+
+// A tuning knob of the tools' benchmarks: the value of an environment variable, at most `cap`.
+inline uint32_t knob(const char *name, uint32_t dflt, uint32_t cap) {
+  const char *s = std::getenv(name);
+  if (!s || !*s) return dflt;
+  return static_cast<uint32_t>(std::min<unsigned long>(std::strtoul(s, nullptr, 10), cap));
 }
 
 }  // namespace rows

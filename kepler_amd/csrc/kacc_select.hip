@@ -247,13 +247,15 @@ int kacc_select_above(kacc_ctx *ctx, kacc_table t, uint32_t zone, uint64_t thres
   if ((rc = kacc::rows::resolve(ctx, fn, tab.kind, rows, node_mask, &a.v)) != KACC_OK) return rc;
   if (item_cap && !out_row && !out_slot && !out_node && !out_energy && !out_power)
     return kacc_fail(ctx, KACC_EINVAL, "%s: item_cap %u and no output array", fn, item_cap);
-  KACC_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-  if (rows->n_nodes == 0) {  // no node lists a row
+  if (rows->n_nodes == 0) {  // no node lists a row: no launch, and a pending launch timing stays pending
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    KACC_HIP(ctx, hipSetDevice(ctx->device));
     KACC_HIP(ctx, hipMemsetAsync(node_off, 0, sizeof(uint32_t), st));
     return KACC_OK;
   }
-  kacc::TimingScope timing(ctx);
+  kacc::rows::Call call(ctx, fn);
+  if ((rc = call.open(stream)) != KACC_OK) return rc;
+  hipStream_t st = call.st;
 
   const uint32_t Z = a.v.Z;
   a.words = tab.words;
@@ -272,45 +274,34 @@ int kacc_select_above(kacc_ctx *ctx, kacc_table t, uint32_t zone, uint64_t thres
   // temporaries, stream ordered: the mask, the tile counts, their scan, the scan's tile sums, the node flags
   const uint64_t n = a.tiles + 1ull, scan_tiles = kacc_internal_scan_tiles(n);
   const uint64_t mask_words = static_cast<uint64_t>(a.tiles) * kWords;
-  uint64_t *tmp = nullptr;
-  KACC_HIP(ctx, hipMallocAsync(reinterpret_cast<void **>(&tmp), 8 * (mask_words + 2 * n + scan_tiles) + 4ull * a.v.n_nodes, st));
-  a.mask = tmp;
-  a.cnt = tmp + mask_words;
-  a.off = a.cnt + n;
-  uint64_t *tile_sum = a.off + n;
-  a.v.nflags = reinterpret_cast<uint32_t *>(tile_sum + scan_tiles);
+  uint64_t *tile_sum = nullptr;
+  kacc::plan::Layout tmp;
+  tmp.add(&a.mask, mask_words);
+  for (uint64_t **p : {&a.cnt, &a.off}) tmp.add(p, n);
+  tmp.add(&tile_sum, scan_tiles);
+  tmp.add(&a.v.nflags, a.v.n_nodes);
+  if ((rc = call.alloc(tmp)) != KACC_OK) return rc;
 
-  (void)hipGetLastError();  // clear a stale error of an earlier call
   const dim3 node_grid(static_cast<uint32_t>((a.v.n_nodes + 1ull + kThreads - 1) / kThreads)), block(kThreads);
-  KACC_LAUNCH(kacc::rows::node_prep_kernel<kThreads>, node_grid, block, 0, st, a.v, a.err, kErrSelect, a.cnt + a.tiles);
-  if (a.tiles) {
-    if (tab.src == kDerived)
-      KACC_LAUNCH(count_kernel<kDerived>, dim3(a.tiles), block, 0, st, a);
-    else if (tab.src == kStored)
-      KACC_LAUNCH(count_kernel<kStored>, dim3(a.tiles), block, 0, st, a);
+  kacc::rows::launch_node_prep<kThreads>(a.v, a.err, kErrSelect, a.cnt + a.tiles, st);
+  if (a.tiles)
+    kacc::rows::dispatch_src(tab.src, [&](auto s) { KACC_LAUNCH(count_kernel<s()>, dim3(a.tiles), block, 0, st, a); });
+  if ((rc = kacc_internal_scan_u64(ctx, a.cnt, n, tile_sum, a.off, st)) != KACC_OK) return rc;
+  if (a.tiles && item_cap) {
+    // 16-B copies for an even Z when the caller's arrays allow them (the tables are hipMalloc'ed)
+    const bool wide = Z % 2 == 0 &&
+                      ((reinterpret_cast<uintptr_t>(out_energy) | reinterpret_cast<uintptr_t>(out_power)) & 15u) == 0;
+    if (a.v.derived && wide)
+      KACC_LAUNCH((scatter_kernel<true, 2>), dim3(a.tiles), block, 0, st, a);
+    else if (a.v.derived)
+      KACC_LAUNCH((scatter_kernel<true, 1>), dim3(a.tiles), block, 0, st, a);
+    else if (wide)
+      KACC_LAUNCH((scatter_kernel<false, 2>), dim3(a.tiles), block, 0, st, a);
     else
-      KACC_LAUNCH(count_kernel<kEnergy>, dim3(a.tiles), block, 0, st, a);
+      KACC_LAUNCH((scatter_kernel<false, 1>), dim3(a.tiles), block, 0, st, a);
   }
-  rc = kacc_internal_scan_u64(ctx, a.cnt, n, tile_sum, a.off, st);
-  if (rc == KACC_OK) {
-    if (a.tiles && item_cap) {
-      // 16-B copies for an even Z when the caller's arrays allow them (the tables are hipMalloc'ed)
-      const bool wide = Z % 2 == 0 &&
-                        ((reinterpret_cast<uintptr_t>(out_energy) | reinterpret_cast<uintptr_t>(out_power)) & 15u) == 0;
-      if (a.v.derived && wide)
-        KACC_LAUNCH((scatter_kernel<true, 2>), dim3(a.tiles), block, 0, st, a);
-      else if (a.v.derived)
-        KACC_LAUNCH((scatter_kernel<true, 1>), dim3(a.tiles), block, 0, st, a);
-      else if (wide)
-        KACC_LAUNCH((scatter_kernel<false, 2>), dim3(a.tiles), block, 0, st, a);
-      else
-        KACC_LAUNCH((scatter_kernel<false, 1>), dim3(a.tiles), block, 0, st, a);
-    }
-    KACC_LAUNCH(node_off_kernel, node_grid, block, 0, st, a);
-    if (hipGetLastError() != hipSuccess) rc = kacc_fail(ctx, KACC_EHIP, "%s: launch", fn);
-  }
-  (void)hipFreeAsync(tmp, st);
-  return rc;
+  KACC_LAUNCH(node_off_kernel, node_grid, block, 0, st, a);
+  return call.finish();
 }
 
 }  // extern "C"

@@ -384,11 +384,9 @@ int fill_args(kacc_ctx *ctx, const char *fn, kacc_table t, uint32_t zone, uint32
 template <int kOut>
 void launch_rows(const Args &a, uint32_t grid, hipStream_t st) {
   using namespace kacc::top;
-  switch (a.mode) {
-    case kEnergy: KACC_LAUNCH((select_kernel<kEnergy, kOut>), dim3(grid), dim3(threads_of(kOut)), 0, st, a); break;
-    case kStored: KACC_LAUNCH((select_kernel<kStored, kOut>), dim3(grid), dim3(threads_of(kOut)), 0, st, a); break;
-    default: KACC_LAUNCH((select_kernel<kDerived, kOut>), dim3(grid), dim3(threads_of(kOut)), 0, st, a); break;
-  }
+  kacc::rows::dispatch_src(a.mode, [&](auto s) {
+    KACC_LAUNCH((select_kernel<s(), kOut>), dim3(grid), dim3(threads_of(kOut)), 0, st, a);
+  });
 }
 
 }  // namespace
@@ -399,20 +397,18 @@ int kacc_top_nodes(kacc_ctx *ctx, kacc_table t, uint32_t zone, uint32_t k, const
                    uint32_t *out_count, uint32_t *out_row, uint32_t *out_slot, uint64_t *out_value, void *stream) {
   if (!ctx) return KACC_EINVAL;
   Args a;
-  const int rc = fill_args(ctx, "kacc_top_nodes", t, zone, k, rows, out_count, out_row, &a);
+  kacc::rows::Call call(ctx, "kacc_top_nodes");
+  int rc = fill_args(ctx, call.fn, t, zone, k, rows, out_count, out_row, &a);
   if (rc != KACC_OK) return rc;
   if (a.v.n_nodes == 0) return KACC_OK;
   if (a.v.n_nodes > 0x7fffffffu) return kacc_fail(ctx, KACC_EINVAL, "kacc_top_nodes: too many nodes for one launch");
-  KACC_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-  kacc::TimingScope timing(ctx);
+  if ((rc = call.open(stream)) != KACC_OK) return rc;
   a.group = 1;
   a.out_count = out_count;
   a.out_row = out_row;
   a.out_slot = out_slot;
   a.out_value = out_value;
-  (void)hipGetLastError();
-  launch_rows<kacc::top::kNodes>(a, a.v.n_nodes, st);
+  launch_rows<kacc::top::kNodes>(a, a.v.n_nodes, call.st);
   KACC_HIP(ctx, hipGetLastError());
   return KACC_OK;
 }
@@ -423,30 +419,22 @@ int kacc_top_fleet(kacc_ctx *ctx, kacc_table t, uint32_t zone, uint32_t k, const
   using namespace kacc::top;
   if (!ctx) return KACC_EINVAL;
   Args a;
-  const int rc = fill_args(ctx, "kacc_top_fleet", t, zone, k, rows, out_count, out_row, &a);
-  if (rc != KACC_OK) return rc;
-  KACC_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-  kacc::TimingScope timing(ctx);
+  kacc::rows::Call call(ctx, "kacc_top_fleet");
+  int rc = fill_args(ctx, call.fn, t, zone, k, rows, out_count, out_row, &a);
+  if (rc != KACC_OK || (rc = call.open(stream)) != KACC_OK) return rc;
+  hipStream_t st = call.st;
   // stage 1 leaves L1 lists in A; the passes of stage 2 alternate between B and A
   const uint32_t fan = std::max(kMinFan, (2 * kBuf + k - 1) / k);  // >= 4096 candidates per workgroup
   const uint64_t L1 = (static_cast<uint64_t>(a.v.n_nodes) + kGroup - 1) / kGroup;
   const uint64_t L2 = (L1 + fan - 1) / fan;
   const uint64_t ents = (L1 + L2) * k, lists = L1 + L2;
-  char *tmp = nullptr;
-  KACC_HIP(ctx, hipMallocAsync(reinterpret_cast<void **>(&tmp), std::max<uint64_t>(ents * 16 + lists * 4, 16), st));
-  Cand A, B;
-  A.ikey = reinterpret_cast<uint2 *>(tmp);
-  B.ikey = A.ikey + L1 * k;
-  A.row = reinterpret_cast<uint32_t *>(tmp + ents * 8);
-  B.row = A.row + L1 * k;
-  A.node = A.row + ents;
-  B.node = A.node + L1 * k;
-  A.count = A.node + ents;
-  B.count = A.count + L1;
-  // as everywhere in the library: an earlier sticky launch error is dropped here, so the
-  // check after the launches (below, after the stream-ordered free) reports these alone
-  (void)hipGetLastError();
+  Cand A;  // both stages' lists: B's follow A's in every array
+  kacc::plan::Layout tmp;
+  tmp.add(&A.ikey, ents);
+  for (uint32_t **p : {&A.row, &A.node}) tmp.add(p, ents);
+  tmp.add(&A.count, lists);
+  if ((rc = call.alloc(tmp, 16)) != KACC_OK) return rc;
+  const Cand B{A.ikey + L1 * k, A.row + L1 * k, A.node + L1 * k, A.count + L1};
   if (L1) {
     a.group = kGroup;
     a.out = A;
@@ -473,7 +461,6 @@ int kacc_top_fleet(kacc_ctx *ctx, kacc_table t, uint32_t zone, uint32_t k, const
   a.out_node = out_node;
   a.out_value = out_value;
   KACC_LAUNCH((select_kernel<kCand, kFleet>), dim3(1), dim3(threads_of(kFleet)), 0, st, a);
-  (void)hipFreeAsync(tmp, st);
   KACC_HIP(ctx, hipGetLastError());
   return KACC_OK;
 }

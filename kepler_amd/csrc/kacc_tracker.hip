@@ -379,10 +379,7 @@ struct kacc_tracker {
 namespace {
 
 void kind_tables(const kacc_ctx *ctx, kacc_kind k, const uint64_t **e, const double **p) {
-  const int base = k == KACC_KIND_PROC ? KACC_T_PROC_ENERGY
-                   : k == KACC_KIND_CTR ? KACC_T_CTR_ENERGY
-                   : k == KACC_KIND_VM ? KACC_T_VM_ENERGY
-                                       : KACC_T_POD_ENERGY;
+  const int base = kacc::kind_energy_table(k);
   *e = static_cast<const uint64_t *>(ctx->tables[base]);
   // a process's (container's, VM's) power is derived (kacc_derive.hpp) from its
   // ratio and its node's tables of the same interval: the tracker must run before

@@ -38,7 +38,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 
 #include "kacc_internal.hpp"
 #include "kacc_rows.hpp"
@@ -53,13 +52,15 @@ constexpr uint32_t kReadPer = 4;                        // read: rows per lane a
 constexpr uint32_t kReadTile = kThreads * kReadPer;
 constexpr uint32_t kSmallWords = 4096;                  // u64 of LDS bins: 32 KiB, three workgroups per CU
 constexpr uint32_t kBigWords = 9984;                    // 78 KiB, two workgroups per CU: 1,996 groups at Z = 4
+static_assert(kSmallWords == plan::kWindowLds.small_words && kBigWords == plan::kWindowLds.big_words,
+              "the host plans the read with the kernels' LDS sizes");
 constexpr uint32_t kRetireThreads = 1024;               // retire: 16 waves, each takes a node at a time
 constexpr uint32_t kRetireWaves = kRetireThreads / 64;
 constexpr uint32_t kRetireGrid = 128;                   // retire: persistent workgroups while the bins are in LDS
 constexpr uint32_t kWaveSum = 8;                        // retire: lanes of one group at or past this add up in the wave
 constexpr uint32_t kMergeRounds = 4;                    // retire: groups tried for that per 64 slots (the digit merges' four)
 constexpr uint32_t kErrGroup = 1u << 13;                // "group sums": a slot, an id, a count or a row range past its range
-using rows::kCus, rows::kMaxCopies, rows::lds_add;
+using rows::kCus, rows::lds_add;
 using u64x2 = __attribute__((ext_vector_type(2))) unsigned long long;
 
 struct State {  // a window's arrays and the records of its kind
@@ -382,26 +383,15 @@ struct kacc_window {
 
 namespace {
 
-// A tuning knob of tools/bench_window.py: the value of an environment variable, at most `cap`
-// (kacc_gtop.hip's idiom).
-inline uint32_t knob(const char *name, uint32_t dflt, uint32_t cap) {
-  const char *s = std::getenv(name);
-  if (!s || !*s) return dflt;
-  return static_cast<uint32_t>(std::min<unsigned long>(std::strtoul(s, nullptr, 10), cap));
-}
-
 kacc::win::State window_state(const kacc_window *w) {
   const kacc_ctx *ctx = w->ctx;
-  const bool pod = w->kind == KACC_KIND_POD;
-  const int te = pod ? KACC_T_POD_ENERGY : w->kind == KACC_KIND_PROC ? KACC_T_PROC_ENERGY
-                 : w->kind == KACC_KIND_CTR ? KACC_T_CTR_ENERGY : KACC_T_VM_ENERGY;
   kacc::win::State s{};
   s.base = w->d_base;
   s.slot_group = w->d_group;
   s.retired = w->d_retired;
   s.retired_count = w->d_rcount;
-  s.tab_e = static_cast<const uint64_t *>(ctx->tables[te]);
-  s.tab_stride = pod ? 2 * w->Z : w->Z;
+  s.tab_e = static_cast<const uint64_t *>(ctx->tables[kacc::kind_energy_table(w->kind)]);
+  s.tab_stride = w->kind == KACC_KIND_POD ? 2 * w->Z : w->Z;
   s.Z = w->Z;
   s.n_groups = w->n_groups;
   s.cap = w->cap;
@@ -428,8 +418,7 @@ int kacc_window_create(kacc_ctx *ctx, kacc_kind kind, uint32_t n_groups, kacc_wi
   *out = nullptr;
   int rc = kacc::rows::resolve_kind(ctx, fn, kind);
   if (rc != KACC_OK) return rc;
-  if (n_groups < 1 || n_groups > KACC_GROUP_MAX)
-    return kacc_fail(ctx, KACC_EINVAL, "%s: n_groups %u outside 1 .. %u", fn, n_groups, KACC_GROUP_MAX);
+  if ((rc = kacc::rows::check_groups(ctx, fn, n_groups)) != KACC_OK) return rc;
   KACC_HIP(ctx, hipSetDevice(ctx->device));
   auto *w = new kacc_window;
   w->ctx = ctx;
@@ -437,11 +426,9 @@ int kacc_window_create(kacc_ctx *ctx, kacc_kind kind, uint32_t n_groups, kacc_wi
   w->kind = kind;
   w->n_groups = n_groups;
   w->Z = ctx->cfg.zones;
-  w->merge_rounds = knob("KACC_WINDOW_MERGE_ROUNDS", kacc::win::kMergeRounds, 64u);
-  w->cap = kind == KACC_KIND_PROC ? ctx->cfg.proc_slots
-           : kind == KACC_KIND_CTR ? ctx->cfg.ctr_slots
-           : kind == KACC_KIND_VM ? ctx->cfg.vm_slots
-                                  : ctx->cfg.pod_slots;
+  // a knob of tools/bench_window.py
+  w->merge_rounds = kacc::rows::knob("KACC_WINDOW_MERGE_ROUNDS", kacc::win::kMergeRounds, 64u);
+  w->cap = kacc::kind_cap(ctx, kind);
   // slots x (base 8Z + id 4): refuse before the allocation when it cannot fit, with the cost in
   // the message (the groups' accumulators are at most 2.3 MB)
   const size_t Z = w->Z, S = static_cast<size_t>(w->cap), per = 8 * Z + 4;
@@ -501,18 +488,16 @@ int kacc_window_step(kacc_window *w, const kacc_top_rows *rows, const uint32_t *
     return kacc_fail(ctx, KACC_EINVAL, "%s: term_count without a slot map or term_slot", fn);
   if (m && (m->ctx != ctx || m->kind != w->kind))
     return kacc_fail(ctx, KACC_EINVAL, "%s: window and slot map differ in context or kind", fn);
-  KACC_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-  kacc::TimingScope timing(ctx);
+  kacc::rows::Call call(ctx, fn);
+  if ((rc = call.open(stream)) != KACC_OK) return rc;
+  hipStream_t st = call.st;
   a.w = window_state(w);
   a.group = group;
   a.assign_all = flags & KACC_WINDOW_ASSIGN_ALL;
   const uint32_t tiles = a.v.n_nodes ? kacc::rows::tiles_of(a.v.n_rows, kAdoptTile) : 0u;  // without a node no row is listed
-  uint32_t *nflags = nullptr;
-  if (tiles) KACC_HIP(ctx, hipMallocAsync(reinterpret_cast<void **>(&nflags), 4ull * a.v.n_nodes, st));
-  a.v.nflags = nflags;
-  (void)hipGetLastError();  // clear a stale error of an earlier call
-  const dim3 block(kThreads);
+  kacc::plan::Layout tmp;
+  if (tiles) tmp.add(&a.v.nflags, a.v.n_nodes);
+  if ((rc = call.alloc(tmp)) != KACC_OK) return rc;
   if (term_count && m->n_nodes) {  // (a) before (b): stream order
     RetireArgs r{a.w, m->n_nodes, m->d_slot_off, term_slot, term_count, w->merge_rounds};
     const uint32_t wgs = (m->n_nodes + kRetireWaves - 1) / kRetireWaves;  // one node per wave
@@ -522,13 +507,10 @@ int kacc_window_step(kacc_window *w, const kacc_top_rows *rows, const uint32_t *
       KACC_LAUNCH(retire_kernel<false>, dim3(wgs), dim3(kRetireThreads), 0, st, r);
   }
   if (tiles) {
-    KACC_LAUNCH(kacc::rows::node_prep_kernel<kThreads>, dim3((a.v.n_nodes + kThreads - 1) / kThreads), block, 0, st, a.v,
-                a.w.err, kErrGroup, static_cast<uint64_t *>(nullptr));
-    KACC_LAUNCH(adopt_kernel, dim3(tiles), block, 0, st, a);
+    kacc::rows::launch_node_prep<kThreads>(a.v, a.w.err, kErrGroup, nullptr, st);
+    KACC_LAUNCH(adopt_kernel, dim3(tiles), dim3(kThreads), 0, st, a);
   }
-  if (hipGetLastError() != hipSuccess) rc = kacc_fail(ctx, KACC_EHIP, "%s: launch", fn);
-  if (nflags) (void)hipFreeAsync(nflags, st);
-  return rc;
+  return call.finish();
 }
 
 int kacc_window_mark(kacc_window *w, void *stream) {
@@ -536,15 +518,14 @@ int kacc_window_mark(kacc_window *w, void *stream) {
   const char *fn = "kacc_window_mark";
   if (!w) return KACC_EINVAL;
   kacc_ctx *ctx = w->ctx;
-  KACC_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-  kacc::TimingScope timing(ctx);
+  kacc::rows::Call call(ctx, fn);
+  if (const int rc = call.open(stream)) return rc;
+  hipStream_t st = call.st;
   const State s = window_state(w);
   KACC_HIP(ctx, hipMemsetAsync(w->d_retired, 0, 8 * static_cast<size_t>(w->n_groups) * w->Z, st));
   KACC_HIP(ctx, hipMemsetAsync(w->d_rcount, 0, 4 * static_cast<size_t>(w->n_groups), st));
   const uint64_t words = w->cap * w->Z;
   if (!words) return KACC_OK;
-  (void)hipGetLastError();
   const bool vec = s.tab_stride == s.Z && s.Z % 2 == 0;
   const uint64_t n = vec ? words / 2 : words;
   const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((n + kThreads - 1) / kThreads, kCus * 32ull));
@@ -552,8 +533,7 @@ int kacc_window_mark(kacc_window *w, void *stream) {
     KACC_LAUNCH(mark_kernel<true>, dim3(grid), dim3(kThreads), 0, st, s, n);
   else
     KACC_LAUNCH(mark_kernel<false>, dim3(grid), dim3(kThreads), 0, st, s, n);
-  if (hipGetLastError() != hipSuccess) return kacc_fail(ctx, KACC_EHIP, "%s: launch", fn);
-  return KACC_OK;
+  return call.finish();
 }
 
 int kacc_window_read(kacc_window *w, const kacc_top_rows *rows, const uint32_t *node_mask, uint32_t *out_count,
@@ -568,9 +548,9 @@ int kacc_window_read(kacc_window *w, const kacc_top_rows *rows, const uint32_t *
   if (rc != KACC_OK) return rc;
   if (!out_count && !out_running && !out_retired && !out_retired_count && !out_total && !out_row)
     return kacc_fail(ctx, KACC_EINVAL, "%s: no output array", fn);
-  KACC_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-  kacc::TimingScope timing(ctx);
+  kacc::rows::Call call(ctx, fn);
+  if ((rc = call.open(stream)) != KACC_OK) return rc;
+  hipStream_t st = call.st;
   a.w = window_state(w);
   const uint32_t Z = a.w.Z, G = a.w.n_groups, W = 1u + Z;
   a.tiles = a.v.n_nodes ? kacc::rows::tiles_of(a.v.n_rows, kReadTile) : 0u;  // without a node no row is listed
@@ -583,61 +563,35 @@ int kacc_window_read(kacc_window *w, const kacc_top_rows *rows, const uint32_t *
 
   // the bins: replicated while they fit the small LDS size, else one copy in the large one, else
   // the accumulator itself
-  const uint32_t stride = (G * W) | 1u;  // odd: the copies of a bin fall into different banks
-  uint32_t lds = 0;
-  a.copies = 1;
-  a.copy_stride = G * W;
-  if (stride <= kSmallWords) {
-    lds = kSmallWords;
-    a.copy_stride = stride;
-    while (a.copies < kMaxCopies && 2 * a.copies * stride <= kSmallWords) a.copies *= 2;
-  } else if (G * W <= kBigWords) {
-    lds = kBigWords;
-  }
-  a.splits = std::max(1u, std::min(a.tiles, kCus * (lds == kBigWords ? 2u : lds ? 3u : 8u)));
+  const kacc::plan::Bins b = kacc::plan::window_bins(G, Z);
+  a.copies = b.copies;
+  a.copy_stride = b.regime == kacc::plan::kSmall ? (G * W) | 1u : G * W;  // odd: the copies of a bin fall into different banks
+  a.splits = kacc::plan::plan_splits(b, a.tiles, 0u);
 
   // temporaries, stream ordered: the accumulator and the node flags
-  const uint64_t acc_words = static_cast<uint64_t>(G) * W;
-  uint64_t *tmp = nullptr;
-  KACC_HIP(ctx, hipMallocAsync(reinterpret_cast<void **>(&tmp), 8 * acc_words + 4ull * a.v.n_nodes, st));
-  a.acc = tmp;
-  a.v.nflags = reinterpret_cast<uint32_t *>(tmp + acc_words);
-  if (hipMemsetAsync(a.acc, 0, 8 * acc_words, st) != hipSuccess) rc = kacc_fail(ctx, KACC_EHIP, "%s: memset", fn);
+  kacc::plan::Layout tmp;
+  tmp.add(&a.acc, static_cast<uint64_t>(G) * W, true);
+  tmp.add(&a.v.nflags, a.v.n_nodes);
+  if ((rc = call.alloc(tmp)) != KACC_OK) return rc;
   // rows of a batch without a node: no tile writes them
-  if (rc == KACC_OK && out_row && !a.tiles && a.v.n_rows &&
-      hipMemsetAsync(out_row, 0, 8ull * a.v.n_rows * Z, st) != hipSuccess)
-    rc = kacc_fail(ctx, KACC_EHIP, "%s: memset", fn);
+  if (out_row && !a.tiles && a.v.n_rows && hipMemsetAsync(out_row, 0, 8ull * a.v.n_rows * Z, st) != hipSuccess)
+    return kacc_fail(ctx, KACC_EHIP, "%s: memset", fn);
 
-  if (rc == KACC_OK) {
-    (void)hipGetLastError();  // clear a stale error of an earlier call
-    const dim3 block(kThreads), grid(a.splits);
-    if (a.tiles) {
-      KACC_LAUNCH(kacc::rows::node_prep_kernel<kThreads>, dim3((a.v.n_nodes + kThreads - 1) / kThreads), block, 0, st, a.v,
-                  a.w.err, kErrGroup, static_cast<uint64_t *>(nullptr));
-      const bool z4 = Z == 4;
-      if (lds == kSmallWords) {
-        if (z4)
-          KACC_LAUNCH((read_kernel<4, kSmallWords>), grid, block, 0, st, a);
-        else
-          KACC_LAUNCH((read_kernel<0, kSmallWords>), grid, block, 0, st, a);
-      } else if (lds == kBigWords) {
-        if (z4)
-          KACC_LAUNCH((read_kernel<4, kBigWords>), grid, block, 0, st, a);
-        else
-          KACC_LAUNCH((read_kernel<0, kBigWords>), grid, block, 0, st, a);
-      } else {
-        if (z4)
-          KACC_LAUNCH((read_kernel<4, 0>), grid, block, 0, st, a);
-        else
-          KACC_LAUNCH((read_kernel<0, 0>), grid, block, 0, st, a);
-      }
-    }
-    const uint64_t words = static_cast<uint64_t>(G) * Z;
-    KACC_LAUNCH(finish_kernel, dim3(static_cast<uint32_t>((words + kThreads - 1) / kThreads)), block, 0, st, a);
-    if (hipGetLastError() != hipSuccess) rc = kacc_fail(ctx, KACC_EHIP, "%s: launch", fn);
+  const dim3 block(kThreads), grid(a.splits);
+  if (a.tiles) {
+    kacc::rows::launch_node_prep<kThreads>(a.v, a.w.err, kErrGroup, nullptr, st);
+    kacc::rows::dispatch_zones(Z, [&](auto z) {
+      if (b.regime == kacc::plan::kSmall)
+        KACC_LAUNCH((read_kernel<z(), kSmallWords>), grid, block, 0, st, a);
+      else if (b.regime == kacc::plan::kBig)
+        KACC_LAUNCH((read_kernel<z(), kBigWords>), grid, block, 0, st, a);
+      else
+        KACC_LAUNCH((read_kernel<z(), 0>), grid, block, 0, st, a);
+    });
   }
-  (void)hipFreeAsync(tmp, st);
-  return rc;
+  const uint64_t words = static_cast<uint64_t>(G) * Z;
+  KACC_LAUNCH(finish_kernel, dim3(static_cast<uint32_t>((words + kThreads - 1) / kThreads)), block, 0, st, a);
+  return call.finish();
 }
 
 int kacc_window_download(kacc_window *w, uint64_t first, uint64_t count, uint64_t *host_base, uint32_t *host_group) {

@@ -18,6 +18,7 @@ from kepler_amd import accel, fleet
 from kepler_amd.torch_batch import current_stream_handle, interval_from_tensors, to_device, top_rows_from_tensors
 from oracle.gofmt import label_pairs, sample_line, watts
 from oracle.oracle import Oracle
+from plan_ref import group_regime  # kacc_group.hip's LDS plan, restated
 
 pytestmark = pytest.mark.gpu
 
@@ -27,6 +28,9 @@ NONE = accel.KACC_GROUP_NONE
 SENT64 = 0x5A5A5A5A5A5A5A5A  # output pre-fill
 SENT32 = 0x5A5A5A5A
 N_GROUPS = [1, 2, 63, 1000, 1025, 4097, 65536]
+# at Z = 5 none of those takes the one-copy regime (the any-Z kernel in the large LDS size): the
+# smallest count that does
+Z5_BIG = 373
 PATTERNS = ["one", "mod", "random", "node"]
 OUT_NAMES = ["count", "energy", "power_fx", "power", "dropped"]
 
@@ -45,6 +49,13 @@ def gpu_ready():
     assert torch.cuda.is_available(), "GPU tests need an MI355X"
     accel.load()
     torch.cuda.set_stream(torch.cuda.Stream())  # every call below runs on a non-default stream
+
+
+def test_the_group_counts_cross_every_regime():
+    for zones, regimes in ((4, ["small", "small", "small", "big", "big", "pass", "pass"]),
+                           (5, ["small", "small", "small", "pass", "pass", "pass", "pass"])):
+        assert [group_regime(g, zones)[2] for g in N_GROUPS] == regimes
+    assert group_regime(Z5_BIG - 1, 5)[2] == "small" and group_regime(Z5_BIG, 5) == (1, 1, "big")
 
 
 def make(name, seed=7, **sim_args):
@@ -154,7 +165,7 @@ def test_sums_equal_the_contract_over_the_oracle(name, kind):
         rows = top_rows_from_tensors(t, KINDS[kind])
         if name == "aligned" and kind == "proc":
             assert rows.n_rows == 4096  # two whole tiles
-        for n_groups in N_GROUPS:
+        for n_groups in N_GROUPS + ([Z5_BIG] if name == "z5" else []):
             for pattern in PATTERNS:
                 group = group_ids(pattern, a[f"{kind}_off"], n_groups, rng)
                 o = run_group(acc, kind, rows, group, n_groups, s)

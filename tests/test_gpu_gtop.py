@@ -17,6 +17,7 @@ from gtop_ref import group_top, merge_shards
 from kepler_amd import accel, fleet
 from kepler_amd.torch_batch import current_stream_handle, interval_from_tensors, to_device, top_rows_from_tensors
 from oracle.oracle import Oracle
+from plan_ref import gtop_regime as regime  # kacc_gtop.hip's counter plan, restated
 from test_gpu_group import KINDS, dev_u32, group_ids, make, run_group, run_intervals
 from test_gpu_quant import run_quant
 from test_gpu_top import run_top
@@ -29,22 +30,9 @@ FILL = 0xFFFFFFFF
 SENT32, SENT64 = 0x5A5A5A5A, 0x5A5A5A5A5A5A5A5A  # output pre-fill: neither a result nor the fill
 OUT_NAMES = ["count", "row", "slot", "node", "value"]
 
-# kacc_gtop.hip's capacities, restated: 256 u32 counters per group, 16384 words of LDS; a wave
-# sorts a segment of at most 64 entries, a workgroup one of at most KACC_TOP_MAX
-DIGITS, LDS_WORDS, MAX_COPIES, WAVE_K = 256, 16384, 64, 64
-
-
-def regime(n_groups):
-    """(copies, where) the library picks: copies > 1 = replicated LDS counters, (1, "lds") = one
-    copy, (0, "global") = global atomics."""
-    words = n_groups * DIGITS
-    if words > LDS_WORDS:
-        return 0, "global"
-    copies = 1
-    if 2 * (words | 1) <= LDS_WORDS:
-        while copies < MAX_COPIES and 2 * copies * (words | 1) <= LDS_WORDS:
-            copies *= 2
-    return copies, "lds"
+# kacc_gtop.hip's, restated: a wave sorts a segment of at most 64 entries, a workgroup one of at
+# most KACC_TOP_MAX
+WAVE_K = 64
 
 
 def sorter(k):

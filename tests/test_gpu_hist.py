@@ -19,6 +19,7 @@ from hist_ref import bound_keys, group_hist
 from kepler_amd import accel, fleet
 from kepler_amd.torch_batch import current_stream_handle, interval_from_tensors, to_device, top_rows_from_tensors
 from oracle.oracle import Oracle
+from plan_ref import MAX_COPIES, hist_regime as regime  # kacc_hist.hip's LDS plan, restated
 from test_gpu_group import FLEETS, KINDS, dev_u32, group_ids, make, run_group, run_intervals
 from top_ref import sort_key
 
@@ -28,26 +29,6 @@ NONE = accel.KACC_GROUP_NONE
 SENT64 = 0x5A5A5A5A5A5A5A5A  # output pre-fill
 OUT_NAMES = ["bin", "cum", "sum", "nan", "unsummed"]
 PATTERNS = ["one", "mod", "random", "node"]
-
-# kacc_hist.hip's LDS capacities in u32 words, restated; a group takes n_bounds + 5 of them
-SMALL_WORDS, BIG_WORDS, PASS_WORDS, MAX_COPIES = 8192, 20096, 19200, 64
-
-
-def regime(n_groups, n_bounds):
-    """(copies, passes) the library picks: copies > 1 = replicated counters in the small LDS size,
-    (1, 1) = one copy (small or large), passes > 1 = the row-word passes."""
-    c = n_bounds + 3
-    per = ((n_groups * c) | 1) + 2 * (n_groups | 1)
-    if per <= SMALL_WORDS:
-        copies = 1
-        while copies < MAX_COPIES and 2 * copies * per <= SMALL_WORDS:
-            copies *= 2
-        return copies, 1, "small"
-    if n_groups * (c + 2) <= BIG_WORDS:
-        return 1, 1, "big"
-    per_pass = PASS_WORDS // (c + 2)
-    return 1, -(-n_groups // per_pass), "pass"
-
 
 # (n_groups, n_bounds); group is NULL for the first
 SHAPES = [(1, 1), (1, 64), (2, 3), (63, 7), (1000, 15), (1025, 64), (16131, 64), (65536, 15),

@@ -18,6 +18,7 @@ from hist_ref import bound_keys
 from kepler_amd import accel
 from kepler_amd.torch_batch import current_stream_handle, interval_from_tensors, to_device, top_rows_from_tensors
 from oracle.oracle import Oracle
+from plan_ref import quant_regime as regime  # kacc_quant.hip's counter plan, restated
 from quant_ref import EMPTY_NAN, group_quantiles
 from test_gpu_group import KINDS, dev_u32, group_ids, make, run_group, run_intervals
 from test_gpu_hist import run_hist
@@ -30,23 +31,6 @@ OUT_NAMES = ["count", "nan", "lo", "hi", "weight", "value"]
 PHI5 = [0.0, 0.5, 0.9, 0.99, 1.0]
 PHI1 = [1.0 / 3.0]
 PHI8 = [0.5, 0.0, 1.0, 0.99, 0.9, 1.0 / 3.0, 0.25, 0.75]
-
-# kacc_quant.hip's capacities, restated: 256 u32 counters per query, 16384 words of LDS
-DIGITS, LDS_WORDS, MAX_COPIES = 256, 16384, 64
-
-
-def regime(n_groups, n_phi):
-    """(copies, where) the library picks: copies > 1 = replicated LDS counters, (1, "lds") = one
-    copy, (0, "global") = global atomics."""
-    words = n_groups * n_phi * DIGITS
-    if words > LDS_WORDS:
-        return 0, "global"
-    copies = 1
-    if 2 * (words | 1) <= LDS_WORDS:
-        while copies < MAX_COPIES and 2 * copies * (words | 1) <= LDS_WORDS:
-            copies *= 2
-    return copies, "lds"
-
 
 # (n_groups, n_phi); group is NULL for n_groups 1
 SHAPES = [(1, 1), (1, 8), (65536, 1), (8192, 8), (7, 1), (3, 5),
